@@ -1,16 +1,26 @@
 #!/usr/bin/env python3
 """bench.py -- train rays/sec of the EO-NeRF hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python bench.py --gpus N --steps K --warmup W            (N > 1 without a launcher: starts the N ranks itself, self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline and nothing else: set-up, the conditioning phase, W warm-up steps, EXACTLY K timed steps of
+configs[2] (below), the result line.  --full adds everything else this script measures: the second configuration (`rgb`), the clock
+probe around the timed bracket, the untimed per-kernel pass and its roofline, the export-render precisions, the CPU baseline and, at
+N > 1, the stand-alone all-reduce latency and the A/B of the exchange's two orders.  --dump-outputs DIR writes what the LAST timed step
+of the headline computed (loss, per-ray outputs, updated parameters and Adam moments; float32 .npy files), through the product path.
+Its inputs are the same in every run and every build: the backward flushes gradients with atomics, whose rounding differs from run to
+run and which a trajectory of Adam steps amplifies far past rounding, so with --dump-outputs the LAST timed step starts from the seeded
+initial parameters and optimizer state (three device copies and a weight re-pack queued in front of it, no host sync) and only that one step's rounding
+can differ.  EONERF_DETERMINISTIC=1 (the library's fixed-order sums; slower) is honoured if the caller sets it: `config.deterministic`.
 
 A step = one complete optimisation step of the launcher's loop (eonerf_code_amd/train_dp.py) on rays that are already
 resident in HBM: the batch of the GPU-resident, per-epoch shuffled ray table (RayTable.batch) -> render forward (sampler
 with in-kernel jitter, fused MLP chain, compositing, shading) -> loss -> backward (compositing, backward chain,
 weight-gradient GEMM) -> [RCCL all-reduce of the flat gradient] -> Adam + weight re-pack.
 
-ONE run measures both single-GPU configurations of BASELINE.json, each with W warm-up steps and EXACTLY K timed steps
+With --full, ONE run measures both single-GPU configurations of BASELINE.json, each with W warm-up steps and EXACTLY K timed steps
 bracketed by barrier + synchronize (max over ranks; HIP events at the boundaries of three blocks inside the bracket give the run's
 own spread):
   `value`, `ms_per_step`, `roofline`, `config.workload`
@@ -20,7 +30,7 @@ own spread):
   `rgb`                        configs[1]: the same rays with the shadow pass off (epoch_idx < 2, MSE loss)
 Weak scaling: per-GPU work is fixed, rays are independent units.
 
-Kernel times come from a SECOND, untimed pass of K steps with the library's HIP-event scopes on -- one scope per kernel launch, on
+With --full, kernel times come from a SECOND, untimed pass of K steps with the library's HIP-event scopes on -- one scope per kernel launch, on
 the stream the kernels run on (the timed passes run without them); every scope is priced with the FLOPs of exactly the layers
 that launch evaluates (kernel_model), so the scopes' FLOPs add up to the step's useful work.  `roofline` prices the dominant kernel against the bound SURVEY.md 8(d) names (bf16 MFMA peak) from its
 ALGORITHMIC FLOPs (8(d): 2 x MACs of the layers it evaluates x live samples) and also carries the HBM view of the same
@@ -248,12 +258,23 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--workload", choices=("both", "rgb", "full"), default="both",
-                    help="both: the full EO-NeRF configuration (configs[2]) as the headline + the sigma+albedo configuration (configs[1]) under \"rgb\"")
+    ap.add_argument("--workload", choices=("both", "rgb", "full"), default=None,
+                    help="both: the full EO-NeRF configuration (configs[2]) as the headline + the sigma+albedo configuration (configs[1]) under \"rgb\" "
+                         "(default: both with --full, full without)")
     ap.add_argument("--precision", choices=("bf16", "fp32"), default="bf16")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-pass", action="store_true", help="skip the untimed per-kernel event pass (rocprof runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: rgb configuration, clock probe, per-kernel pass and roofline, "
+                         "export renders, CPU baseline, N > 1 all-reduce latency and exchange A/B")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the headline's last timed step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if args.workload is None:
+        args.workload = "both" if args.full else "full"
+    deterministic = os.environ.get("EONERF_DETERMINISTIC", "0") not in ("", "0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process becomes the launcher -- BEFORE any HIP call (a process that has
@@ -288,7 +309,8 @@ def main():
     torch.manual_seed(42)                                     # train_eonerf.py:37
     field = EONerfMLP(N_IMG, radiometric_normalization=True, precision=args.precision).to(dev)
     trainer = FusedTrainer(field, lr=5e-4, max_rays=RAYS, keep_message=os.environ.get("EONERF_KEEP_MESSAGE") == "1")
-    trainer.set_noise_seed(1000 + 7919 * rank)
+    noise_seed = 1000 + 7919 * rank
+    trainer.set_noise_seed(noise_seed)
     # the GPU-resident ray table of the launcher (every rank holds the whole table and walks its slice of one shared permutation)
     table = RayTable(*synthetic_batch(RAYS * TABLE_BATCHES * world, N_IMG, seed=1234), dev, seed=42, rank=rank, world=world)
     spe = table.steps_per_epoch(RAYS)
@@ -306,6 +328,18 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    def dump_outputs(out_dir, loss):
+        """What a caller of the timed path holds after its last step: the loss, the per-ray outputs of the render (trainer.out, columns of
+        sat_rendering.py:311), the updated parameters (the flat buffer every parameter is a view of) and the Adam moments; ~11 MB."""
+        arrays = {"loss": loss.detach().reshape(1), "ray_outputs": trainer.out[:RAYS], "params": trainer.flat,
+                  "adam_exp_avg": trainer.exp_avg, "adam_exp_avg_sq": trainer.exp_avg_sq}
+        arrays = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrays.items()}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        os.makedirs(out_dir, exist_ok=True)
+        import numpy as np
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+
     peak = PEAK_BF16_TFLOPS if args.precision == "bf16" else PEAK_FP32_TFLOPS
     elt = 2 if args.precision == "bf16" else 4
 
@@ -313,9 +347,12 @@ def main():
         """DECLARED conditioning phase, in front of the W warm-up steps and outside every timed region: untimed steps in event-timed blocks
         of 10 until three consecutive blocks agree within 1 % (cap 300 steps).  A fresh process on a fresh box starts its first kernels
         while the chip is still leaving its idle power state ("the stall of BENCH_r04"); `steps`, `warmup` and the K-step mean
-        are exactly what the command line says.  EONERF_BENCH_CONDITION=0 switches it off.  Returns (steps run, block means in ms)."""
+        are exactly what the command line says.  EONERF_BENCH_CONDITION=0 switches it off.  Returns (steps run, block means in ms).
+        Its number of steps depends on the chip, so it leaves no trace: parameters, Adam state and the jitter stream are put back as they
+        were, and the warm-up starts at `first_step` -- the steps behind it see the same inputs whatever the conditioning did."""
         if os.environ.get("EONERF_BENCH_CONDITION", "1") == "0":
             return 0, [], None
+        saved = (trainer.flat.clone(), trainer.exp_avg.clone(), trainer.exp_avg_sq.clone(), trainer.step_count)
         blocks, n, first = [], 0, None
         while n < 300:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -339,12 +376,27 @@ def main():
             blocks.append(ms)
             if len(blocks) >= 3 and max(blocks[-3:]) <= 1.01 * min(blocks[-3:]):
                 break
+        torch.cuda.synchronize()
+        restore(saved)
+        trainer.set_noise_seed(noise_seed)       # restarts the in-kernel jitter stream and drops a presampled batch
         return n, blocks, first
+
+    def restore(state):
+        """Put parameters and Adam state back to a snapshot (queued on the stream: no host sync); the next step re-packs the weights."""
+        with torch.no_grad():
+            trainer.flat.copy_(state[0])
+            trainer.exp_avg.copy_(state[1])
+            trainer.exp_avg_sq.copy_(state[2])
+        trainer.step_count = state[3]
+        field._packed_version = None             # the next step re-packs the restored weights (eonerf_set_weights)
+        field.weights_changed_natively()
 
     def measure(wl, first_step):
         epoch_idx = 3 if wl == "full" else 0
+        dump = args.dump_outputs and wl == workloads[0]
+        if dump:      # the seeded initial state: the dumped last timed step starts from it
+            initial = (trainer.flat.clone(), trainer.exp_avg.clone(), trainer.exp_avg_sq.clone(), trainer.step_count)
         cond_steps, cond_blocks, cond_first = conditioning(first_step, epoch_idx)
-        first_step += cond_steps
         if world > 1:
             # the serial tail of a step (all-reduce + Adam + re-pack, event to event) is sampled over the W WARM-UP steps, behind the
             # conditioning phase: the timed steps carry no events but their one boundary mark (an event pair costs microseconds of queue time)
@@ -367,7 +419,7 @@ def main():
         trainer.hidden_events = None
         trainer.tail_events, trainer.presample_events = None, []
         trainer.check_device_status()                           # a hand-off fault of the warm-up would have switched paths: report it here
-        probe_pre = trainer.clock_probe()                       # fixed MFMA loop: the clock the chip holds going into the bracket
+        probe_pre = trainer.clock_probe() if args.full else None        # fixed MFMA loop: the clock the chip holds going into the bracket
         # EXACTLY K timed steps between two barrier + synchronize brackets; one HIP event per step boundary (recorded on the stream, no host
         # sync inside the timed region), so that a slow step is visible -- and attributable -- from the JSON line alone
         blocks = split_blocks(args.steps)
@@ -378,13 +430,17 @@ def main():
         marks[0].record()
         for i in range(args.steps):
             h0 = time.perf_counter()
+            if dump and i == args.steps - 1:
+                restore(initial)
             loss = one_step(first_step + args.warmup + i, epoch_idx)
             marks[i + 1].record()
             host_ms.append((time.perf_counter() - h0) * 1e3)
         barrier()
         dt = time.perf_counter() - t0
         trainer.check_device_status()                           # every rank: a faulted step would have been skipped, not timed as work
-        probe_post = trainer.clock_probe()
+        if dump and rank == 0:
+            dump_outputs(args.dump_outputs, loss)
+        probe_post = trainer.clock_probe() if args.full else None
         if world > 1:
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -397,7 +453,8 @@ def main():
                            "first": step_ms[0], "all": [round(x, 3) for x in step_ms] if args.steps <= 256 else None, "host_enqueue_ms_max": max(host_ms), "host_enqueue_ms_p50": statistics.median(host_ms),
                            "note": "HIP events between the K timed steps (GPU time from the end of one step to the end of the next)"},
                "clock_probe": {"before_mhz": probe_pre["mhz"], "after_mhz": probe_post["mhz"], "before_us": probe_pre["us"], "after_us": probe_post["us"],
-                               "note": "fixed MFMA loop outside the bracket (eonerf_clock_probe): shader clock from s_memtime / s_memrealtime"},
+                               "note": "fixed MFMA loop outside the bracket (eonerf_clock_probe): shader clock from s_memtime / s_memrealtime"}
+                              if args.full else None,
                "conditioning_steps": cond_steps, "conditioning_blocks_ms_per_step": cond_blocks, "conditioning_first_block_step_ms": cond_first,
                "step_tail_us": tail_us,
                "step_tail_presample_us": tail_pre_us, "exchange_hidden_us": hidden_us, "exchange_early_us": early_us}
@@ -408,7 +465,7 @@ def main():
         rec["camera_samples_per_step"], rec["sun_samples_per_step"] = n_cam, n_sun
         # ---- untimed pass: the same steps with the library's per-kernel HIP-event scopes (on the stream the kernels run on) ----
         kernels = {}
-        if not args.no_kernel_pass:
+        if args.full and not args.no_kernel_pass:
             trainer.profile_enable(args.steps)
             for i in range(args.steps):
                 one_step(first_step + args.warmup + args.steps + i, epoch_idx)
@@ -433,7 +490,7 @@ def main():
             rec["kernel_flop_sum"] = sum(k["algorithmic_flop_per_launch"] for k in kernels.values())
         # ---- N > 1, untimed: the SAME steps with the other order of the gradient exchange (one all-reduce behind the backward against the
         #      early block from the library's event), alternating -- the A/B only a multi-GPU box can run; nothing of it is in `value` ----
-        if trainer._exchanges() and wl == workloads[0] and os.environ.get("EONERF_BENCH_EXCHANGE_AB", "1") != "0":
+        if args.full and trainer._exchanges() and wl == workloads[0] and os.environ.get("EONERF_BENCH_EXCHANGE_AB", "1") != "0":
             default_buckets, ab, nxt = trainer.buckets, {"one_bucket": [], "two_buckets": []}, first_step + args.warmup + 2 * args.steps
             try:
                 for _ in range(2):
@@ -491,7 +548,7 @@ def main():
         return rec
 
     # headline = configs[2], the full EO-NeRF step (what the reference runs for all but its first two epochs, sat_rendering.py:269-276);
-    # configs[1] (shadow pass off) rides along under "rgb"
+    # with --full, configs[1] (shadow pass off) rides along under "rgb"
     workloads = ("full", "rgb") if args.workload == "both" else (args.workload,)
     recs, first = {}, 0
     for wl in workloads:
@@ -500,8 +557,9 @@ def main():
             r_ = recs[wl]
             print(f"[bench] {wl}: {r_['rays_per_s']:.0f} rays/s, {r_['ms_per_step']:.3f} ms/step "
                   f"(blocks {', '.join(f'{b:.3f}' for b in r_['blocks_ms_per_step'])}; step min/p50/max {r_['step_ms']['min']:.3f}/{r_['step_ms']['p50']:.3f}/"
-                  f"{r_['step_ms']['max']:.3f} @ {r_['step_ms']['argmax']}; clock {r_['clock_probe']['before_mhz']:.0f} -> {r_['clock_probe']['after_mhz']:.0f} MHz; "
-                  f"conditioning {r_['conditioning_steps']} steps {[round(b, 3) for b in r_['conditioning_blocks_ms_per_step']]})", file=sys.stderr, flush=True)
+                  f"{r_['step_ms']['max']:.3f} @ {r_['step_ms']['argmax']}; "
+                  + (f"clock {r_['clock_probe']['before_mhz']:.0f} -> {r_['clock_probe']['after_mhz']:.0f} MHz; " if r_['clock_probe'] else "")
+                  + f"conditioning {r_['conditioning_steps']} steps {[round(b, 3) for b in r_['conditioning_blocks_ms_per_step']]})", file=sys.stderr, flush=True)
         first += recs[wl]["conditioning_steps"] + args.warmup + 2 * args.steps
     dist_info = None
     if world > 1:
@@ -512,18 +570,21 @@ def main():
         dist.all_gather_object(ids, {"rank": rank, "device": str(dev), "pid": os.getpid(),
                                      "uuid": str(getattr(torch.cuda.get_device_properties(dev), "uuid", ""))})
         msg = torch.zeros_like(trainer.d_flat)
-        lat = []
-        for i in range(60):
-            barrier()
-            t0 = time.perf_counter()
-            dist.all_reduce(msg, op=dist.ReduceOp.SUM)
-            torch.cuda.synchronize()
-            if i >= 10:
-                lat.append((time.perf_counter() - t0) * 1e6)
-        t = torch.tensor([statistics.median(lat)], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        allreduce_us = None
+        if args.full:
+            lat = []
+            for i in range(60):
+                barrier()
+                t0 = time.perf_counter()
+                dist.all_reduce(msg, op=dist.ReduceOp.SUM)
+                torch.cuda.synchronize()
+                if i >= 10:
+                    lat.append((time.perf_counter() - t0) * 1e6)
+            t = torch.tensor([statistics.median(lat)], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            allreduce_us = t.item()
         dist_info = {"ranks_seen": dist.get_world_size(), "backend": dist.get_backend(), "devices": ids,
-                     "allreduce_us": t.item(), "allreduce_bytes": msg.numel() * 4,
+                     "allreduce_us": allreduce_us, "allreduce_bytes": msg.numel() * 4,
                      # rank 0's median over the W warm-up steps (behind the conditioning phase) of the headline workload: gradient all-reduce (side stream) + Adam + re-fold /
                      # re-pack, event to event -- the part of a step that no ray work overlaps
                      "step_tail_us": recs[workloads[0]].get("step_tail_us"),
@@ -565,7 +626,7 @@ def main():
             "config": {"workload": names[workloads[0]], "rays_per_gpu": RAYS, "n_samples": 128, "n_images": N_IMG, "parallelism": f"dp{world}",
                        "batching": "GPU-resident ray table, shuffled on the device once per epoch, batches = slices (RayTable.batch); in-kernel Philox jitter",
                        "camera_samples_per_step": head["camera_samples_per_step"], "sun_samples_per_step": head["sun_samples_per_step"],
-                       "final_loss": head["final_loss"]},
+                       "final_loss": head["final_loss"], "deterministic": deterministic},
             "blocks_ms_per_step": head["blocks_ms_per_step"], "median_block_ms_per_step": head["median_block_ms_per_step"],
             "step_ms": head["step_ms"], "clock_probe": head["clock_probe"], "conditioning_steps": head["conditioning_steps"],
             "conditioning_blocks_ms_per_step": head["conditioning_blocks_ms_per_step"],
@@ -579,9 +640,9 @@ def main():
             result[wl] = nested(wl)
         if world > 1:
             result["dist"] = dist_info
-        if world == 1 and args.precision == "bf16" and not args.no_kernel_pass:
+        if args.full and world == 1 and args.precision == "bf16" and not args.no_kernel_pass:
             result["export_render"] = export_bench(field, table, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(workloads)
         print(json.dumps(result))
     if world > 1:

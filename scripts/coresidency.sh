@@ -17,7 +17,7 @@ cd ../..
 run() {  # label, lib, env...
   local label=$1 lib=$2; shift 2
   for i in 1 2; do
-    env "$@" EONERF_LIB=$lib timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload full 2> /tmp/cor.err | python3 -c "
+    env "$@" EONERF_LIB=$lib timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload full 2> /tmp/cor.err | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.readline()); k = d['kernels']
 print('$label run $i: step %.3f ms | pipe_cam %.4f pipe_sun %.4f wgrad %.4f heads %.4f fwd %.4f+%.4f' % (d['ms_per_step'], k['bwd_pipe_camera']['avg_ms'], k['bwd_pipe_sun']['avg_ms'], k['wgrad_gemm']['avg_ms'], k['bwd_chain_camera']['avg_ms'], k['fwd_chain_camera']['avg_ms'], k['fwd_chain_sun']['avg_ms']))"

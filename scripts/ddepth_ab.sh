@@ -11,7 +11,7 @@ cd ../..
 B=$PWD/eonerf_code_amd/csrc/build
 EONERF_LIB=$B/libeonerf_vd2.so timeout -k 10 400 python -m pytest tests/test_bwd_pipe.py -m gpu -q -x 2>&1 | tail -3
 run() {
-  EONERF_LIB=$2 timeout -k 10 200 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
+  EONERF_LIB=$2 timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
 import json, sys
 try:
     d = json.loads(sys.stdin.readline()); k = d['kernels']

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/dw16; rm -rf $O; mkdir -p $O; cd $R
 for V in base dw16 base dw16; do
   L=$R/eonerf_code_amd/csrc/libeonerf_hip.so; [ $V = dw16 ] && L=$R/ab_libs/libeonerf_dw16.so
   export EONERF_LIB=$L
-  python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-kernel-pass --workload full 2>&1 | grep "^\[bench\]" | sed "s/^/$V /"
+  python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-kernel-pass --workload full 2>&1 | grep "^\[bench\]" | sed "s/^/$V /"
   rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_$V -o prof -- python3 bench.py --steps 6 --warmup 3 --workload full --no-cpu-baseline --no-kernel-pass > /dev/null 2> $O/pmc_$V.err
 done
 python3 - <<PY

@@ -7,7 +7,7 @@ for N in "$@"; do $HC -DEO_EP_ABL=$N -c eonerf_enc_pair.hip -o build/ep_v$N.o &&
 cd ../..
 for N in 0 "$@"; do
   LIB=""; [ "$N" != "0" ] && LIB=$PWD/eonerf_code_amd/csrc/build/libeonerf_vep$N.so
-  EONERF_LIB=$LIB timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
+  EONERF_LIB=$LIB timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
 import json, sys
 try:
     d = json.loads(sys.stdin.readline()); k = d['kernels']

@@ -10,7 +10,7 @@ mk spread "-DEO_PIPE_SPREAD=1"
 cd ../..
 B=$PWD/eonerf_code_amd/csrc/build
 run() {
-  EONERF_LIB=$2 timeout -k 10 200 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
+  EONERF_LIB=$2 timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
 import json, sys
 try:
     d = json.loads(sys.stdin.readline()); k = d['kernels']

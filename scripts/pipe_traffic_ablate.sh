@@ -12,7 +12,7 @@ cd ../..
 B=$PWD/eonerf_code_amd/csrc/build
 for N in 0 "$@" 0; do
   LIB=""; [ "$N" != "0" ] && LIB=$B/libeonerf_vt$N.so
-  EONERF_LIB=$LIB timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
+  EONERF_LIB=$LIB timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
 import json, sys
 try:
     d = json.loads(sys.stdin.readline()); k = d['kernels']

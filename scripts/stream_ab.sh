@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/stream_ab; mkdir -p $O; cd $R
 for rep in 1 2; do
 for S in ${SWEEP:-0 4 18 32 46}; do
-  EONERF_PIPE_STREAM=$S python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --workload ${WL:-full} 2> /dev/null | python3 -c "
+  EONERF_PIPE_STREAM=$S python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --workload ${WL:-full} 2> /dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 k = d['kernels']

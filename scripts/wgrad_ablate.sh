@@ -14,7 +14,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/wgrad_ablate; mkdir -p $O; cd $R
 for N in 0 1 2 4 8 3 5 6 7 0; do
   L=$R/eonerf_code_amd/csrc/libeonerf_hip.so; [ $N != 0 ] && L=$R/ab_libs/libeonerf_wgabl$N.so
   for WL in full rgb; do
-  EONERF_LIB=$L EONERF_BENCH_CONDITION=0 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload $WL 2> /dev/null | python3 -c "
+  EONERF_LIB=$L EONERF_BENCH_CONDITION=0 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload $WL 2> /dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 print('abl $N (1 no flush, 2 no mfma, 4 no dma, 8 no barrier) $WL: wgrad %.4f ms' % d['kernels']['wgrad_gemm']['avg_ms'])

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/wgrad_jobs; mkdir -p $O; cd $R
   && /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o build/libeonerf_mask.so $(ls build/*.o | grep -v eonerf_api.o | grep -v api_mask.o | grep -v abl | grep -v stamp) build/api_mask.o) || exit 1
 export EONERF_LIB=$R/eonerf_code_amd/csrc/build/libeonerf_mask.so
 for M in 0x7ff 0x1 0x4 0x8 0x10 0x70 0x80 0x100 0x400 0x3 0x300 0xf8 0x704; do
-  EONERF_WGRAD_MASK=$M python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
+  EONERF_WGRAD_MASK=$M python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 print('mask $M: wgrad %.4f ms  (step %.3f)' % (d['kernels']['wgrad_gemm']['avg_ms'], d['ms_per_step']))

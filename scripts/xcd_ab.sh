@@ -14,7 +14,7 @@ mk ring8nt "-DEO_RING_USE=8 -DEO_XCD_NT=1"
 cd ../..
 B=$PWD/eonerf_code_amd/csrc/build
 run() { # label lib xcd
-  EONERF_LIB=$2 EONERF_PIPE_XCD=$3 timeout -k 10 200 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
+  EONERF_LIB=$2 EONERF_PIPE_XCD=$3 timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --workload full 2> /dev/null | python3 -c "
 import json, sys
 try:
     d = json.loads(sys.stdin.readline()); k = d['kernels']

@@ -1,9 +1,14 @@
 import os
 import sys
 
-import numpy as np
-import pytest
-import torch
+# MKL picks its sgemm code path by CPU model, and the fp32 gradients of the oracle-vs-golden tests amplify that rounding past their
+# bounds; the COMPATIBLE branch gives the same bits on every x86 CPU (tests/golden/make_golden.py writes the goldens under it too).
+# Read when MKL initialises, so it is set before torch is imported.
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
+import torch  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:

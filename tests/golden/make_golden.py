@@ -18,8 +18,10 @@ import os
 import sys
 import types
 
-import numpy as np
-import torch
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")      # the same MKL code path on every CPU, as tests/conftest.py sets it
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))

@@ -207,7 +207,7 @@ def test_bench_gpus_2_launches_its_own_ranks():
     import json
     env = dict(os.environ, EONERF_BENCH_REHEARSAL="1", EONERF_PIPE="0")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-pass",
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-kernel-pass",
                         "--workload", "rgb"], cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
