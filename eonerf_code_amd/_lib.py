@@ -56,7 +56,7 @@ def build(verbose=False):
             return hashlib.sha1(fh.read()).hexdigest()
 
     # the stamp names the sources AND the library build() itself produced from them with the Makefile's own flags: a library that was
-    # rebuilt by hand afterwards (an ablation build: make CXXFLAGS=... -DEO_ABL=..) does not match it and is rebuilt from scratch
+    # rebuilt by hand afterwards (a diagnostic build: make CXXFLAGS=... -DEO_STAMP) does not match it and is rebuilt from scratch
     recorded = open(stamp).read().split() if os.path.exists(stamp) else []
     if not os.environ.get("EONERF_LIB") and os.path.exists(LIB_PATH) and len(recorded) == 2 and recorded[0] == digest:
         if recorded[1] == so_digest():

@@ -14,9 +14,6 @@
 #include "eonerf_carve.h"
 #include <math.h>
 #include <stdio.h>
-#ifdef EO_COR
-hipError_t eo_launch_cor_partner(const void* src, size_t total_bytes, size_t stream_bytes, int n_wg, hipStream_t st);
-#endif
 
 #define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
 
@@ -30,7 +27,6 @@ struct DevStream {
 
 }  // namespace
 
-constexpr int PIPE_STREAM_DEFAULT = 0;      // (A/B: scripts/stream_ab.sh)
 constexpr int RANGE_WORD = 16;      // ctx->dev_status[RANGE_WORD]: fp16 x 3 range flag (a cache line of its own; eonerf_range_status)
 constexpr int RANGE_STICKY_WORD = 17;   // ... and the WEIGHT criteria of the last re-pack: reported like RANGE_WORD, cleared only by the next eonerf_set_weights
 constexpr int DIGEST_WORD = 32;     // ctx->dev_status[32..35]: two 64-bit ray digests (eonerf_rays.h: ray_word_digest) -- [0] what eonerf_presample's
@@ -46,13 +42,10 @@ struct eonerf_ctx {
     int pipe_xcd = 0;       // XCD-local pipelines of the pipelined backward (EONERF_PIPE_XCD; BwdPipeArgs::xcd_local)
     int stagger = 0;        // wave stagger of the chain kernels (EONERF_STAGGER; MlpFwdArgs::stagger)
     int wgrad_riders = 1;   // EONERF_WGRAD_RIDERS=0: the sigma row and the embedding columns as jobs of their own (A/B switch)
-    int wgrad_items;      // target number of weight-gradient work items per launch (EONERF_WGRAD_ITEMS, default 48 per job)
     ParamLayout pl;
     DevStream fwd_full, fwd_dens, bwd_full, bwd_dens, bwd_rgb, bwd_full_ig, pipe_wt, bwd_full_heads, bwd_rgb_heads, bwd_dens_heads, ig_tail_wt;
     bool pipe = false;               // layer-pipelined trunk backward (bf16 camera pass; EONERF_PIPE=0 switches back to chain + GEMM)
     int n_pipes = 0;
-    int stream_blocks = 0;           // EONERF_PIPE_STREAM: workgroups of the pipelined CAMERA launch that run ready weight-gradient GEMM items
-    int n_pipes_stream = 0;          // ... and the pipelines that launch keeps: (CUs - stream_blocks) / 7
     float* loss_scratch = nullptr;   // [LOSS_MAX_BLOCKS] per-block partial sums of k_loss + its arrival counter (self-resetting: no memset per step)
     float* fold = nullptr;           // [FOLD_FLOATS (+ 256 x 256: W_bott transposed, for the backward's tail kernel)] fp32: the heads' first layers folded with the bottleneck layer (eonerf_pack.h), re-computed
                                      // by k_fold in front of every re-pack
@@ -64,8 +57,7 @@ struct eonerf_ctx {
     std::unordered_map<const void*, bool> ws_pipe;
     int pipe_fault_stage = -1;       // test hook (EONERF_PIPE_FAULT)
     bool deterministic = false;      // EONERF_DETERMINISTIC=1: every atomic flush of the backward is replaced by partials + a fixed-order sum
-    bool pipe_partials = false;      // the pipelined launches flush their stationary dW through partial buffers + a reduction kernel (always
-                                     // in deterministic mode; EONERF_PIPE_PARTIALS=1 alone: A/B switch against the atomic flush)
+                                     // (the pipelined launches: partial buffers + a reduction kernel)
     unsigned long long* pipe_stamps = nullptr;   // diagnostics (EONERF_PIPE_STAMPS=1): cycle sums per stage, read by eonerf_debug_pipe_stamps
     uint64_t noise_seed = 0x5eed5eedULL; uint32_t noise_call = 0;   // in-kernel Philox jitter (eonerf_set_noise_seed)
     // eonerf_presample: the camera sampler of the NEXT training forward already ran (under the gradient exchange of the step before);
@@ -94,7 +86,7 @@ namespace {
 
 CarveCfg carve_cfg(const eonerf_ctx* ctx) {
     CarveCfg c;
-    c.bf16 = ctx->bf16; c.pipe = ctx->pipe; c.deterministic = ctx->deterministic; c.pipe_partials = ctx->pipe_partials;
+    c.bf16 = ctx->bf16; c.pipe = ctx->pipe; c.deterministic = ctx->deterministic; c.pipe_partials = ctx->deterministic;
     c.n_pipes = ctx->n_pipes; c.n_samples = ctx->n_samples;
     c.enc_part_wgs = (ctx->enc_pair && ctx->pipe && !ctx->deterministic) ? ctx->n_cu : 0;
     return c;
@@ -388,15 +380,13 @@ inline int pipe_spare_cus(const eonerf_ctx* ctx) {
 
 // trunk layers 7..1 of one pass: dX chain + weight gradients.  Reads dY_7 from w.pipe.dy_in (written by the heads chain or the heads
 // pipeline), accumulates dW / db of the trunk into d_flat, saves dY_5 / dY_0 in b.grd.
-struct WgradPlan;
-int fill_stream_args(const eonerf_ctx* ctx, const WgradPlan& plan, int* queue, int* stop, PipeStreamArgs& sa);
 int run_bwd_pipe(eonerf_ctx* ctx, const RenderWs& w, const PassBuffers& b, int p_cap, float* d_flat, int prof_id, hipStream_t st, int slot, bool first_of_backward,
-                 const AmbientBwdArgs* amb = nullptr, const WgradPlan* plan = nullptr) {
+                 const AmbientBwdArgs* amb = nullptr) {
     const ParamLayout& pl = ctx->pl;
     { const int rc = pipe_clear(w, first_of_backward, slot, st); if (rc) return rc; }
     ProfScope ps(ctx, prof_id, st);
     BwdPipeArgs pa;
-    pipe_common(ctx, w, b, p_cap, d_flat, slot, plan ? ctx->n_pipes_stream : ctx->n_pipes, PIPE_STAGES, pa);
+    pipe_common(ctx, w, b, p_cap, d_flat, slot, ctx->n_pipes, PIPE_STAGES, pa);
     pa.wt = ctx->pipe_wt.data; pa.dy_in = w.pipe.dy_in;
     pa.xcd_local = ctx->pipe_xcd;
     pa.fault_stage = ctx->pipe_fault_stage; pa.stamps = ctx->pipe_stamps;
@@ -405,41 +395,6 @@ int run_bwd_pipe(eonerf_ctx* ctx, const RenderWs& w, const PassBuffers& b, int p
         const int l = 7 - s;
         pa.dw_off[s] = pl.t[pl.trunk_w[l]].offset; pa.db_off[s] = pl.t[pl.trunk_b[l]].offset; pa.dw_ld[s] = l == 5 ? 319 : 256;
     }
-    if (plan) {      // streaming roles: ready items of the weight-gradient GEMM under the stages
-        PipeStreamArgs sa;
-        uint32_t* sync = w.pipe.sync + (size_t)slot * (w.pipe.sync_bytes / sizeof(uint32_t));
-        const int rcs = fill_stream_args(ctx, *plan, w.queue, reinterpret_cast<int*>(sync) + 48, sa);      // (word 48 of the launch's zeroed sync header)
-        if (rcs) return rcs;
-        HIP_TRY(eo_launch_bwd_pipe_stream(pa, sa, st));
-        return 0;
-    }
-#ifdef EO_COR
-    // Co-residency falsifier (diagnostic builds only, scripts/coresidency.sh): EONERF_COR_PARTNER=1 launches the dummy streaming partner
-    // (eonerf_bwd_pipe.hip: k_cor_partner) on a side stream BESIDE the camera pass' pipelined launch, =2 on the same stream in front of it
-    // (the partner alone on the chip); EONERF_COR_GB = bytes it streams (default 2 GB, out of the camera pass' activation slab).
-    // Its durations are summed and printed when the process ends.
-    {
-        static const int mode = getenv("EONERF_COR_PARTNER") ? atoi(getenv("EONERF_COR_PARTNER")) : 0;
-        static const double gb = getenv("EONERF_COR_GB") ? atof(getenv("EONERF_COR_GB")) : 2.0;
-        struct Cor { hipStream_t side = nullptr; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; double gb = 0; int mode = 0;
-                     ~Cor() { double ms = 0; int n = 0; for (auto& e : ev) { float t = 0; if (hipEventElapsedTime(&t, e.first, e.second) == hipSuccess) { ms += t; ++n; } }
-                              if (n) fprintf(stderr, "[cor] partner mode %d: %d launches, avg %.4f ms, %.1f GB/s (%.2f GB each)\n", mode, n, ms / n, gb / (ms / n * 1e-3), gb); } };
-        static Cor cor;
-        if (mode && prof_id == EONERF_PROF_BWD_PIPE_CAMERA) {
-            cor.gb = gb; cor.mode = mode;
-            if (!cor.side) HIP_TRY(hipStreamCreateWithFlags(&cor.side, hipStreamNonBlocking));
-            hipEvent_t e0, e1, fork;
-            HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-            hipStream_t ps = mode == 1 ? cor.side : st;
-            if (mode == 1) { HIP_TRY(hipEventCreateWithFlags(&fork, hipEventDisableTiming)); HIP_TRY(hipEventRecord(fork, st)); HIP_TRY(hipStreamWaitEvent(cor.side, fork, 0)); }
-            const size_t slab_bytes = (size_t)p_cap * 2048 * 2;      // (X_1 .. X_8 rows of the camera pass' activation slab: >= 2 GB at 4096 rays)
-            HIP_TRY(hipEventRecord(e0, ps));
-            HIP_TRY(eo_launch_cor_partner(b.act, slab_bytes, (size_t)(gb * 1e9), ctx->n_cu, ps));
-            HIP_TRY(hipEventRecord(e1, ps));
-            if (cor.ev.size() < 4096) cor.ev.push_back({e0, e1});
-        }
-    }
-#endif
     HIP_TRY(eo_launch_bwd_pipe(pa, st));
     if (pa.partials) HIP_TRY(eo_launch_pipe_reduce(pa, st));
     return 0;
@@ -448,33 +403,15 @@ int run_bwd_pipe(eonerf_ctx* ctx, const RenderWs& w, const PassBuffers& b, int p
 // Weight gradients of up to two MLP passes in ONE split-K launch (eonerf_wgrad.hip) + the bottleneck factor product:
 //   full: a pass through the whole field (camera pass / EONerfMLP.forward), with or without the transient head in the graph;
 //   dens: a density-only pass (shadow pass / query_density).  Either may be null.  Gradients are ACCUMULATED into d_flat.
-// plan != nullptr: the table is only BUILT (into plan->tab; the camera pass' layer-0 / skip-column jobs, whose dY_0 / dY_5 operands the
-// pipelined camera launch is still to write, at the END of the queue: plan->ready_items = the items in front of them) -- the caller
-// launches the pipelined trunk with streaming roles on the ready items and then launch_planned_wgrad() for what is left.
-struct WgradPlan { WgradJobTable tab; int ready_items; };
-int fill_stream_args(const eonerf_ctx* ctx, const WgradPlan& plan, int* queue, int* stop, PipeStreamArgs& sa) {
-    if (plan.tab.n > WGRAD_STREAM_JOBS) return EONERF_E_STATE;
-    memset(&sa, 0, sizeof(sa));
-    sa.blocks = ctx->stream_blocks; sa.ready_items = plan.ready_items; sa.queue = queue; sa.stop = stop;
-    for (int i = 0; i < plan.tab.n; ++i) sa.tab.j[i] = plan.tab.j[i];
-    sa.tab.aux = plan.tab.aux; sa.tab.n = plan.tab.n; sa.tab.items = plan.tab.items;
-    return 0;
-}
-int launch_planned_wgrad(eonerf_ctx* ctx, const WgradPlan& plan, int p_cap, int* queue, hipStream_t st) {
-    ProfScope ps(ctx, EONERF_PROF_WGRAD, st);
-    HIP_TRY(eo_launch_wgrad(plan.tab, ctx->n_cu - (ctx->exch_event ? ctx->exch_cus : 0), p_cap, queue, ctx->bf16, st, nullptr, false));
-    return 0;
-}
 int run_weight_gradients(eonerf_ctx* ctx, const float* flat, float* d_flat, const PassBuffers* full, bool transient,
                          const PassBuffers* dens, int p_cap, float* m_bott, int* queue, hipStream_t st, bool full_trunk_done = false,
                          bool dens_trunk_done = false, float* det_partials = nullptr, bool zeroed = false, BottWgradArgs* defer_bott = nullptr,
-                         WgradPlan* plan = nullptr, bool dens_enc_done = false) {
+                         bool dens_enc_done = false) {
     // defer_bott != nullptr: the products that follow from the bottleneck factors are NOT launched here; their arguments are handed back
     // (the render path runs them in one launch with the embedding and ambient-head gradients, eo_launch_step_tail)
     const ParamLayout& pl = ctx->pl;
     auto dptr = [&](int ti) { return d_flat + pl.t[ti].offset; };
     WgradJobTable tab;
-    bool late[WGRAD_MAX_JOBS] = {};      // (plan) jobs whose operands the pipelined camera launch writes
     tab.n = 0;
     memset(&tab.aux, 0, sizeof(tab.aux));
     tab.aux.job = -1;
@@ -501,25 +438,25 @@ int run_weight_gradients(eonerf_ctx* ctx, const float* flat, float* d_flat, cons
     };
     // pipelined: the 256 x 256 products of layers 1..7 (and their biases) were accumulated by the layer-pipelined trunk backward;
     // what is left are the two 256 x 64 products against the encoding (layer 0, skip columns of layer 5) and the sigma row
-    auto trunk_jobs = [&](const PassBuffers& b, bool pipelined, bool sigma_job, bool written_late, bool enc_jobs) {
+    auto trunk_jobs = [&](const PassBuffers& b, bool pipelined, bool sigma_job, bool enc_jobs) {
         // (pipelined: dY_0 and dY_5 lie in their slab tiles in unit order -- written once by the stages of layers 1 and 6)
         // (enc_jobs = false: the two products against the encoding were formed by eo_launch_enc_pair, with the pass' input-gradient tail)
         if (enc_jobs) {
         add(b, GRD_ROW_Y0, 256, ACT_ROW_ENC, 64, dptr(pl.trunk_w[0]), 63, dptr(pl.trunk_b[0]), ctx->enc_colmap, 4, 2, 2, 1);
-        tab.j[tab.n - 1].a_units = pipelined; late[tab.n - 1] = written_late;
+        tab.j[tab.n - 1].a_units = pipelined;
         }
         for (int l = 1; l < 8; ++l) {
             const int in_ld = l == 5 ? 319 : 256;
             if (!pipelined)
                 add(b, GRD_ROW_Y0 + 256 * l, 256, ACT_ROW_X1 + 256 * (l - 1), 256, dptr(pl.trunk_w[l]), in_ld, dptr(pl.trunk_b[l]), nullptr, 2, 4, 4, 2);
             if (l == 5 && enc_jobs)   // skip columns 256..318 <- encoding slots
-                { add(b, GRD_ROW_Y0 + 256 * 5, 256, ACT_ROW_ENC, 64, dptr(pl.trunk_w[5]) + 256, 319, nullptr, ctx->enc_colmap, 4, 2, 2, 1); tab.j[tab.n - 1].a_units = pipelined; late[tab.n - 1] = written_late; }
+                { add(b, GRD_ROW_Y0 + 256 * 5, 256, ACT_ROW_ENC, 64, dptr(pl.trunk_w[5]) + 256, 319, nullptr, ctx->enc_colmap, 4, 2, 2, 1); tab.j[tab.n - 1].a_units = pipelined; }
         }
         if (sigma_job) add(b, GRD_ROW_SIG, 1, ACT_ROW_X1 + 256 * 7, 256, dptr(pl.sig_w), 256, dptr(pl.sig_b), nullptr, 1, 8, 1, 1);
     };
     if (full) {
         const PassBuffers& c = *full;
-        trunk_jobs(c, full_trunk_done, !riders, plan != nullptr, true);
+        trunk_jobs(c, full_trunk_done, !riders, true);
         // bottleneck factors M_a = dA1^T X8 (and M_t = dT1^T X8) + the bias gradients db_A1 (db_T1), finished by eo_launch_bott_wgrad
         // below into THREE weight gradients: the bottleneck layer's and the two head layers' that read the bottleneck output (which is
         // therefore never saved by the forward, nor read back here: see BottWgradArgs)
@@ -550,38 +487,16 @@ int run_weight_gradients(eonerf_ctx* ctx, const float* flat, float* d_flat, cons
             split_at(1, dptr(pl.tbe_w), 128, dptr(pl.tbe_b));
         }
     }
-    if (dens) trunk_jobs(*dens, dens_trunk_done, true, false, !dens_enc_done);
-    if (plan) {      // late jobs to the end of the table (stable), the riders' job index follows
-        WgradJob ordered[WGRAD_MAX_JOBS];
-        int k = 0, aux_job = tab.aux.job;
-        for (int pass = 0; pass < 2; ++pass)
-            for (int i = 0; i < tab.n; ++i)
-                if (late[i] == (pass == 1)) { if (i == tab.aux.job) aux_job = k; ordered[k++] = tab.j[i]; }
-        for (int i = 0; i < tab.n; ++i) tab.j[i] = ordered[i];
-        tab.aux.job = aux_job;
-    }
+    if (dens) trunk_jobs(*dens, dens_trunk_done, true, !dens_enc_done);
     // every work item = one slice of one job's sample range, equal slices for every job; persistent workgroups pull items from one
     // counter.  Since the K loop is instantiated per tile shape the launch is HBM-bound (5.7 TB/s) and an item's time follows the
-    // bytes its job moves per K step.  Measured rules (scripts/wgrad_items_sweep.sh; slices in proportion to the bytes were tried
-    // twice and lost to equal slices at every item count):
+    // bytes its job moves per K step.  Measured rules (item-count sweeps through a switch removed after commit 38660b0; slices in
+    // proportion to the bytes were tried twice and lost to equal slices at every item count):
     //   few jobs (the rgb state: 4): the HEAVY jobs' items (>= 45 % of the heaviest job's bytes per step) fill exactly one round,
     //     just under one item per CU, and the light jobs' items fill the gaps behind them: 0.227-0.238 ms at 288-320 items against
     //     0.26 at 512 and 0.28 at 352 (heavy items spill into a second round)
     //   many jobs (the full state with the pipelined trunk: 11): ~2.5 items per CU: flat (0.472-0.478 ms) from 650 to 830 items,
     //     0.49-0.50 at 512-600 and at 1,024
-#ifdef EO_WGRAD_MASK
-    {   // DIAGNOSTIC BUILDS ONLY (scripts/wgrad_jobs.sh builds with -DEO_WGRAD_MASK): EONERF_WGRAD_MASK keeps only the jobs whose bit is set --
-        // gradients are WRONG, timing only.  The shipped library does not read the variable.
-        static const char* mk = getenv("EONERF_WGRAD_MASK");
-        if (mk) {
-            const unsigned long mask = strtoul(mk, nullptr, 0);
-            int k = 0;
-            for (int i = 0; i < tab.n; ++i) if (mask & (1ul << i)) { if (i == tab.aux.job) tab.aux.job = k; else if (k == tab.aux.job && i != k) tab.aux.job = -1; tab.j[k] = tab.j[i]; late[k] = late[i]; ++k; }
-            if (tab.aux.job >= k) tab.aux.job = -1;
-            tab.n = k;
-        }
-    }
-#endif
     double wmax = 0.0, wj[WGRAD_MAX_JOBS];
     for (int k = 0; k < tab.n; ++k) {
         wj[k] = (double)((tab.j[k].m_rows + 15) / 16 * 16 + (tab.j[k].n_rows + 15) / 16 * 16) * SEG_B;
@@ -594,18 +509,12 @@ int run_weight_gradients(eonerf_ctx* ctx, const float* flat, float* d_flat, cons
         WgradJob& j = tab.j[k];
         int fill = (int)(2.54 * ctx->n_cu / tab.n + 0.5);
         if (tab.n <= 8) fill = (ctx->n_cu - 1) / std::max(n_heavy, 1);
-        int sl = ctx->wgrad_items ? (ctx->wgrad_items + tab.n / 2) / tab.n : (tab.n > 16 ? std::max(fill, 48) : std::min(std::max(fill, 1), 256));
+        int sl = tab.n > 16 ? std::max(fill, 48) : std::min(std::max(fill, 1), 256);
         if (det_partials && sl > 48) sl = 48;       // the partial buffer holds WGRAD_MAX_JOBS x 48 items
         j.slices = sl < 1 ? 1 : sl;
     }
     for (int k = 0; k < tab.n; ++k) { tab.j[k].item0 = tab.items; tab.items += tab.j[k].slices; }
-    if (plan) {
-        int n_late = 0;
-        for (int i = 0; i < tab.n; ++i) n_late += late[i] ? 1 : 0;
-        plan->tab = tab;
-        plan->ready_items = tab.n > n_late ? tab.j[tab.n - n_late].item0 : 0;
-        if (n_late == 0) plan->ready_items = tab.items;
-    } else {
+    {
         ProfScope ps(ctx, EONERF_PROF_WGRAD, st);
         HIP_TRY(eo_launch_wgrad(tab, ctx->n_cu - (ctx->exch_event ? ctx->exch_cus : 0), p_cap, queue, ctx->bf16, st, det_partials, !zeroed));
     }
@@ -654,12 +563,10 @@ int eonerf_create(eonerf_ctx** out, const eonerf_config* cfg) {
     ctx->bf16 = cfg->precision == EONERF_BF16;
     const bool infer_only = cfg->precision == EONERF_F16X3;      // forward streams only
     { const char* e = getenv("EONERF_DETERMINISTIC"); ctx->deterministic = e && atoi(e) != 0; }
-    { const char* e = getenv("EONERF_PIPE_PARTIALS"); ctx->pipe_partials = ctx->deterministic || (e && atoi(e) != 0); }
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { delete ctx; return (int)hipErrorNoDevice; }
     ctx->n_cu = prop.multiProcessorCount;
-    { const char* e = getenv("EONERF_WGRAD_ITEMS"); ctx->wgrad_items = e && atoi(e) > 0 ? atoi(e) : 0; }
     { const char* e = getenv("EONERF_WGRAD_RIDERS"); if (e) ctx->wgrad_riders = atoi(e); }
     { const char* e = getenv("EONERF_STAGGER"); if (e) ctx->stagger = atoi(e); }
     { const char* e = getenv("EONERF_PIPE_XCD"); if (e) ctx->pipe_xcd = atoi(e); }
@@ -683,12 +590,6 @@ int eonerf_create(eonerf_ctx** out, const eonerf_config* cfg) {
             if (!eo_bwd_pipe_fits_a_cu() || getenv("HSA_CU_MASK") || getenv("ROC_GLOBAL_CU_MASK")) ctx->pipe = false;
         }
         { const char* fb = getenv("EONERF_PIPE_FALLBACK"); ctx->pipe_fallback = !(fb && atoi(fb) == 0); }
-        {
-            const char* sb = getenv("EONERF_PIPE_STREAM");
-            ctx->stream_blocks = sb ? atoi(sb) : PIPE_STREAM_DEFAULT;
-            if (ctx->stream_blocks < 0 || ctx->stream_blocks > ctx->n_cu - PIPE_STAGES || ctx->deterministic || ctx->pipe_partials) ctx->stream_blocks = 0;
-            ctx->n_pipes_stream = std::min(ctx->n_pipes, (ctx->n_cu - ctx->stream_blocks) / PIPE_STAGES);
-        }
         if (!rc && ctx->pipe) rc = upload(ctx->pipe_wt, build_pipe_stream(ctx->pl));
         if (!rc && ctx->pipe) rc = upload(ctx->bwd_full_heads, build_bwd_stream(ctx->pl, true, true, false, true, 1));
         if (!rc && ctx->pipe) rc = upload(ctx->bwd_rgb_heads, build_bwd_stream(ctx->pl, true, true, false, false, 1));
@@ -1024,29 +925,16 @@ static int camera_backward(eonerf_ctx* ctx, const RenderWs& w, const float* flat
     { ProfScope ps(ctx, EONERF_PROF_BWD_CHAIN_CAMERA, st);
       HIP_TRY(eo_launch_mlp_bwd(mc, ctx->bf16, !density_only, density_only, transient && !density_only, grid, st, pipe ? 1 : 0)); }
     BottWgradArgs bott;
-    const bool stream = pipe && !density_only && ctx->stream_blocks > 0 && !ctx->deterministic && !w.det.wgrad_part && !w.det.pipe_part;
-    if (stream) {
-        // the GEMM's job table first: the pipelined launch hands its ready items to streaming workgroups (PipeStreamArgs), the GEMM launch
-        // behind it takes the rest of the SAME queue (zeroed with the backward's sync block)
-        WgradPlan plan;
-        const int rcw = run_weight_gradients(ctx, flat, d_flat, &w.cam, transient, sun, p_cap, w.m_bott, w.queue, st, true, sun != nullptr, nullptr, true, &bott, &plan, sun_enc_done);
-        if (rcw) return rcw;
-        const int rcp = run_bwd_pipe(ctx, w, w.cam, p_cap, d_flat, EONERF_PROF_BWD_PIPE_CAMERA, st, 1, first_pipe, nullptr, &plan);
-        if (rcp) return rcp;
-        const int rcl = launch_planned_wgrad(ctx, plan, p_cap, w.queue, st);
-        if (rcl) return rcl;
-    } else {
-        if (pipe) {
-            const int rcp = run_bwd_pipe(ctx, w, w.cam, p_cap, d_flat, EONERF_PROF_BWD_PIPE_CAMERA, st, 1, first_pipe); if (rcp) return rcp;
-            // the trunk's pipelined layers are complete in d_flat here (the shadow pass' launch ran before this one)
-            if (ctx->exch_event && !density_only) { HIP_TRY(hipEventRecord(ctx->exch_event, st)); ctx->exch_recorded = true; }
-        }
-        const PassBuffers* full = density_only ? nullptr : &w.cam;
-        const PassBuffers* dens = density_only ? &w.cam : sun;
-        const int rcw = run_weight_gradients(ctx, flat, d_flat, full, transient, dens, p_cap, w.m_bott, w.queue, st, pipe, pipe && dens, w.det.wgrad_part, pipe,
-                                             (full && !ctx->deterministic) ? &bott : nullptr, nullptr, sun_enc_done && !density_only);
-        if (rcw) return rcw;
+    if (pipe) {
+        const int rcp = run_bwd_pipe(ctx, w, w.cam, p_cap, d_flat, EONERF_PROF_BWD_PIPE_CAMERA, st, 1, first_pipe); if (rcp) return rcp;
+        // the trunk's pipelined layers are complete in d_flat here (the shadow pass' launch ran before this one)
+        if (ctx->exch_event && !density_only) { HIP_TRY(hipEventRecord(ctx->exch_event, st)); ctx->exch_recorded = true; }
     }
+    const PassBuffers* full = density_only ? nullptr : &w.cam;
+    const PassBuffers* dens = density_only ? &w.cam : sun;
+    const int rcw = run_weight_gradients(ctx, flat, d_flat, full, transient, dens, p_cap, w.m_bott, w.queue, st, pipe, pipe && dens, w.det.wgrad_part, pipe,
+                                         (full && !ctx->deterministic) ? &bott : nullptr, sun_enc_done && !density_only);
+    if (rcw) return rcw;
     if (density_only) return EONERF_OK;
     if (!ctx->deterministic) {
         // the three independent tails of the backward -- bottleneck-factor products, embedding table, per-ray ambient head -- in ONE launch

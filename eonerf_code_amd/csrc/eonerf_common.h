@@ -22,12 +22,6 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 #define EO_DEV __device__ __forceinline__
 
-// Diagnostic builds only (scripts/ablate.sh): EO_ABL bit 0 drops the per-chunk s_barrier, bit 1 the A-operand LDS re-reads,
-// bit 2 the ReLU/mask work of the epilogues, bit 3 the weight prefetch, bit 4 the HBM traffic of the slab stores.  Results are WRONG with any bit set; the shipped
-// library is built with EO_ABL == 0.
-#ifndef EO_ABL
-#define EO_ABL 0
-#endif
 // EO_STAMP (diagnostic builds only, scripts/stamp.sh): s_memtime stamps around the waits of the chain kernels, summed per wave
 // into eo_stamps[] (total, copy wait, barrier wait, flush wait, waves) and read back by eonerf_debug_read().
 #ifdef EO_STAMP
@@ -199,7 +193,7 @@ template <class P, int SLOT_BYTES> struct WStream {
     EO_DEV void prefetch_next() {
         int nq = q + 1; if (nq == n_chunks) nq = 0;
         const ChunkDesc d = desc(nq);
-        pf_off = d.off; pf_bytes = (EO_ABL & 8) ? 0u : d.bytes; pf_base = 0; pf_slot = par ^ 1;
+        pf_off = d.off; pf_bytes = d.bytes; pf_base = 0; pf_slot = par ^ 1;
     }
     EO_DEV void pump() { if (pf_base < pf_bytes) round(); }
     EO_DEV void pump_rest() { while (pf_base < pf_bytes) round(); }
@@ -224,8 +218,7 @@ template <class P, int SLOT_BYTES> struct WStream {
         par ^= 1;
         return;
 #endif
-        if (EO_ABL & 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(YOUNGER > 63 ? 63 : YOUNGER) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(YOUNGER > 63 ? 63 : YOUNGER) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(YOUNGER > 63 ? 63 : YOUNGER) : "memory");
         q = q + 1; if (q == n_chunks) q = 0;
         par ^= 1;
     }
@@ -236,8 +229,7 @@ template <class P, int SLOT_BYTES> struct WStream {
         for (int i = 0; i < n_chunks; ++i) {
             prefetch_next();
             pump_rest();
-            if (EO_ABL & 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
             q = q + 1; if (q == n_chunks) q = 0;
             par ^= 1;
         }
@@ -256,13 +248,8 @@ template <class P> struct TileSched {
         const int W = (n_pts + P::TILE - 1) / P::TILE * P::WAVES;
         full = W / (P::WAVES * grid);
         const int R = W - full * P::WAVES * grid, q = R / grid, r = R % grid;
-        rem_cnt = (EO_ABL & 32) ? 0 : q + (block < r ? 1 : 0);
+        rem_cnt = q + (block < r ? 1 : 0);
         rem_start = full * P::WAVES * grid + block * q + (block < r ? block : r);
-        if (EO_ABL & 32) {      // diagnostic: the former schedule (whole tiles only)
-            const int tiles = R / P::WAVES;
-            rem_cnt = block < tiles ? P::WAVES : 0;
-            rem_start = (full * grid + block) * P::WAVES;
-        }
     }
     EO_DEV int iters() const { return full + (rem_cnt > 0 ? 1 : 0); }
     // first wave tile and number of waves with samples in iteration `it`
@@ -360,7 +347,7 @@ EO_DEV void chunk_compute(WS& ws, int lane, int h, const BArr& B, int m0, Epi&& 
             const int f = g * KG + kg;
             if (BIAS && g + 1 < G && kg == BPOS) nxt = bias_init(chunk + NF * P::UNIT_B + (g + 1) * 128, h);
             acc = P::mma(fr[f % PF], B(kg), acc);
-            if (!(EO_ABL & 2) && f + PF < NF) fr[f % PF] = lds_unit<P>(a + (f + PF) * P::UNIT_B);
+            if (f + PF < NF) fr[f % PF] = lds_unit<P>(a + (f + PF) * P::UNIT_B);
             if (g == 0) {
                 if (kg == PLAST) ws.pump_rest();
                 else if (kg < PLAST) ws.pump();
@@ -446,7 +433,6 @@ EO_DEV Sl<PBf16> relu_slice(PBf16, const f32x16& acc, int s, uint32_t& bits) {
     const s16x2 z = {0, 0};
     const uint32_t ones = 0x00010001u;
     const uint32_t wi = cvt_pk_bf16(acc[2 * s], acc[2 * s + 1]);
-    if (EO_ABL & 4) return Sl<PBf16>{wi};
     const uint32_t x = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, wi), z));
     uint32_t t;
     asm("v_pk_min_u16 %0, %1, %2" : "=v"(t) : "v"(x), "v"(ones));      // 1 where the element is > 0 (x is >= 0 here)
@@ -552,9 +538,9 @@ constexpr int SEG_B = 64;
 // than the caches hold; with the default policy the write-back traffic held up the chain kernels (measured: forward chain
 // -12 %, backward chain -21 %, and the weight-gradient GEMM that follows -5 %)
 constexpr int SLAB_STORE_POLICY = 2;
-#ifndef EO_ELEM_POLICY
-#define EO_ELEM_POLICY 0      // cache policy of the element-wise slab stores (encoding rows, the heads' scalar gradient rows); nt (2) measured +0.3 % on the step: 2-byte streaming stores
-#endif
+// cache policy of the element-wise slab stores (encoding rows, the heads' scalar gradient rows): default.  nt (2) measured +0.3 % on
+// the step: 2-byte streaming stores (profiles/r05_ab2_cache_policies.txt)
+constexpr int ELEM_STORE_POLICY = 0;
 struct SlabBlk { int s, r; };
 template <class P> struct Slab {
     static constexpr int TSAMP = SEG_B / P::ACT_BYTES;     // samples per segment
@@ -585,7 +571,7 @@ struct SlabWriterBase {
     EO_DEV __amdgpu_buffer_rsrc_t block_rs(SlabBlk b) const {      // descriptor of a whole block (SGPRs)
         return __builtin_amdgcn_make_buffer_rsrc(slab + (size_t)b.s * nt * SEG_B, 0, b.r * nt * SEG_B, 0x00020000);
     }
-    EO_DEV uint32_t block_off(SlabBlk b, int row) const { return (((EO_ABL & 16) ? 0 : tile0) * b.r + (row - b.s)) * SEG_B; }   // EO_ABL 16: every wave writes sample tile 0 (stores stay in L2)
+    EO_DEV uint32_t block_off(SlabBlk b, int row) const { return (tile0 * b.r + (row - b.s)) * SEG_B; }
 };
 
 template <class Map> struct SlabWriter<PH3, Map> : NoSlab {      // never instantiated for training: the hooks of an inference chain
@@ -704,7 +690,7 @@ template <class Map> struct SlabWriter<PBf16, Map> : SlabWriterBase {
     EO_DEV void drain() { flush_store<0>(); flush(); flush(); }
     EO_DEV void elem(int row, float v) const {
         const SlabBlk b = Map::block(row);
-        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)v), block_rs(b), voff1, block_off(b, row), EO_ELEM_POLICY);
+        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)v), block_rs(b), voff1, block_off(b, row), ELEM_STORE_POLICY);
     }
 };
 

@@ -23,12 +23,6 @@
 #include "eonerf_common.h"
 #include "eonerf_kernels.h"
 
-// Diagnostic builds only (scripts/enc_pair_ablate.sh): EO_EP_ABL bit 0 (the atomic flush of the first version) is gone, bit 1 the d enc waves' work (MFMAs + encoder
-// derivative), bit 2 the dW waves' MFMAs and fragment reads, bit 3 the LDS-DMA refill behind the prologue.  Results are WRONG with any bit set.
-#ifndef EO_EP_ABL
-#define EO_EP_ABL 0
-#endif
-
 namespace {
 
 constexpr int NT = 512;
@@ -75,7 +69,6 @@ EO_DEV void enc_waves(const EncPairArgs& a, uint8_t* smem, int lane, int wave, i
         const int slot = (t - t0) & (NS - 1), par = (t - t0) & 1;
         asm volatile("s_barrier" ::: "memory");
         if (wave == 0 && t > t0) finish(t - 1, par ^ 1);
-        if (EO_EP_ABL & 2) continue;
         // ---- d enc partial of (source s_src, m-tile mt): 16 MFMAs over the tile's 16 B units ----
         const uint8_t* bp = smem + slot * SLOT_B + s_src * IMG + lane * 16;
         f32x16 acc = zero_acc();
@@ -159,11 +152,9 @@ EO_DEV void dw_waves(const EncPairArgs& a, uint8_t* smem, int lane, int wave, in
         const int slot = (t - t0) & (NS - 1);
         // this wave's share of step t has landed once at most DEPTH - 1 younger steps are outstanding; the barrier publishes every wave's
         // share and retires all reads of the slot refilled next
-        if (EO_EP_ABL & 8) asm volatile("s_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N_DMA * (DEPTH - 1)) : "memory");
-        if (!(EO_EP_ABL & 8)) issue(t + DEPTH < t1 ? t + DEPTH : t1 - 1, (slot + DEPTH) & (NS - 1));
+        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N_DMA * (DEPTH - 1)) : "memory");
+        issue(t + DEPTH < t1 ? t + DEPTH : t1 - 1, (slot + DEPTH) & (NS - 1));
         const uint8_t* T = smem + slot * SLOT_B;
-        if (EO_EP_ABL & 4) continue;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             // (inline asm: for the intrinsic the wait-count pass assumes aliasing with the LDS-DMA in flight and drains it)

@@ -332,12 +332,7 @@ __global__ void k_table_reduce(const float* contrib, const int64_t* idx, int n_r
 constexpr int BOTT_LDS_F = 256 + 256 * 17;
 // body of one (virtual) block of 256 threads: vblk = block index, j = thread; s_w [256], s_t [256][17].  Every barrier is executed by
 // all threads of the REAL block (two virtual blocks of the same branch share one in the merged tail kernel).
-#ifndef EO_TAIL_SKIP      // diagnostic builds only (results WRONG): bit 0 / 1 / 2 drop the bottleneck-row / head-row / embedding roles of the tail kernel
-#define EO_TAIL_SKIP 0
-#endif
 EO_DEV void bott_wgrad_body(const BottWgradArgs& a, int vblk, int j, float* s_w, float (*s_t)[17]) {
-    if ((EO_TAIL_SKIP & 1) && vblk < 256) return;
-    if ((EO_TAIL_SKIP & 2) && vblk >= 256) return;
     if (vblk < 256) {
         const int i = vblk;
         float acc = 0.f, accb = 0.f;
@@ -505,7 +500,6 @@ __global__ __launch_bounds__(512) void k_step_tail(StepTailArgs a) {
     // (an odd last virtual block runs with an idle partner: rays beyond n_rays are skipped inside)
     // (measured, round 5: these blocks behind the bottleneck products in the SAME workgroups -- one round of 256 instead of 384 workgroups on
     //  256 CUs -- is slower, 23.9 vs 21.4 us: the embedding role is three dependent HBM round trips, better started on a free CU)
-    if (EO_TAIL_SKIP & 4) return;
     emb_grad_body(a.emb, 2 * blk + half, tid, lds + half * (AMB_LDS_F / 2));
 }
 
@@ -628,8 +622,7 @@ hipError_t eo_launch_bott_wgrad(const BottWgradArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 hipError_t eo_launch_ambient_bwd(const AmbientBwdArgs& a, hipStream_t st, bool deterministic) {
-    static int blocks = 0;
-    if (!blocks) { const char* e = getenv("EONERF_AMB_BLOCKS"); blocks = e && atoi(e) > 0 ? atoi(e) : 32; }      // measured (4096 rays): 64 blocks 46 us, 32: 37, 16: 39, 8: 58
+    constexpr int blocks = 32;      // measured (4096 rays): 64 blocks 46 us, 32: 37, 16: 39, 8: 58
     // deterministic mode: ONE block -- every address is then added by exactly one thread, its rays in a fixed order
     const int want = deterministic ? 1 : (a.n_rays + AMB_BATCH - 1) / AMB_BATCH;
     hipLaunchKernelGGL(k_ambient_bwd, dim3(want < blocks ? want : blocks), dim3(128 * AMB_STREAMS), 0, st, a);

@@ -18,7 +18,7 @@ template <class P>
 __global__ __launch_bounds__(WG_NT) void k_wgrad(const WgradJobTable tab, int p_pad, int* queue, float* partials) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     (void)p_pad;
-    wgrad_work<P, WgradJobTable, false>(tab, queue, partials, smem, 0, nullptr);
+    wgrad_work<P>(tab, queue, partials, smem);
 }
 
 // deterministic mode: block = row, thread = column; the jobs one after the other in table order, a job's non-empty slices in slice

@@ -1,21 +1,8 @@
-// Device side of the weight-gradient GEMM (eonerf_wgrad.hip): the work loop as a device function, so that the k_wgrad launch AND the
-// streaming roles of the pipelined trunk backward (eonerf_bwd_pipe.hip: workgroups beyond the stage roles of the camera launch run ready
-// GEMM items under the MFMA-bound stages, which leave half of the HBM bandwidth unused) share one body.
+// Device side of the weight-gradient GEMM (eonerf_wgrad.hip): the work loop of the k_wgrad launch.
 #pragma once
 #include "eonerf_common.h"
 #include "eonerf_kernels.h"
 #include <type_traits>
-
-// Diagnostic builds only (scripts/wgrad_ablate.sh): EO_WG_ABL bit 0 drops the atomic flush of an item's tile, bit 1 the MFMAs, bit 2 the LDS-DMA
-// of the operands (the counted waits then wait for nothing), bit 3 the per-step barrier.  Results are WRONG with any bit set.
-#ifndef EO_WG_ABL
-#define EO_WG_ABL 0
-#endif
-#ifndef EO_WG_DESC
-#define EO_WG_DESC 1
-#endif
-
-#define EO_WG_MMA(a, b, c) ((EO_WG_ABL & 2) ? (c) : P::mma(a, b, c))
 
 namespace eo_wgrad {
 
@@ -37,16 +24,9 @@ EO_DEV int wg_swz(int row, int chunk) { return (chunk ^ ((row >> 2) & 3)) * 16; 
 constexpr int WG_SMEM = NS * SLOT_B + NS * AUX_B + 16;
 
 // The work loop of the weight-gradient GEMM: this workgroup (WG_NT threads, WG_SMEM bytes of LDS at `smem`) pulls (job, K slice) items from
-// `queue` until none is left.  Tab: WgradJobTable (k_wgrad) or WgradJobTableS (the streaming roles of the pipelined launch).
-// BOUNDED (streaming roles of eonerf_bwd_pipe.hip): only items below `ready_items` are claimed (compare-and-swap: an item is never taken
-// and dropped) -- the jobs behind them read operands the surrounding launch is still writing -- and an item is only claimed while it
-// will be done before the launch's stages are: progress[0] = steps the first pipeline's first stage has run (published every 16 steps),
-// progress[1] = the steps it has to run; the role measures its own items (s_memrealtime) and stops claiming when the last one took
-// longer than the stages have left at their rate so far.  What is left goes to the k_wgrad launch that follows, on all CUs.
-template <class P, class Tab, bool BOUNDED>
-EO_DEV void wgrad_work(const Tab& tab, int* queue, float* partials, uint8_t* smem, int ready_items, const int* progress) {
-    const unsigned long long t_role = BOUNDED ? __builtin_amdgcn_s_memrealtime() : 0ull;
-    unsigned long long t_claim = t_role, item_ticks = 0;
+// `queue` until none is left.
+template <class P>
+EO_DEV void wgrad_work(const WgradJobTable& tab, int* queue, float* partials, uint8_t* smem) {
     typedef typename P::U U;
     constexpr int BK = ROW_B / P::ACT_BYTES;             // samples per K step
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5, r = lane & 31;
@@ -57,39 +37,10 @@ EO_DEV void wgrad_work(const Tab& tab, int* queue, float* partials, uint8_t* sme
   // global counter, so slow (latency-bound, few-row) jobs and fast ones balance without any host-side cost model.
   for (;;) {
     __syncthreads();                                    // previous item fully consumed (LDS ring + lds_item)
-    if (tid == 0) {
-        if constexpr (BOUNDED) {
-            int got = -1;
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            if (t_claim != t_role) item_ticks = now - t_claim;      // the item this role has just finished
-            const long long done = __hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const long long total = __hip_atomic_load(progress + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            bool go = true;
-            if (total > 0) {      // (not yet published: the launch has only just started)
-                // stages' time left at their rate so far: (total - done) x elapsed / done; the first item's duration is not known yet:
-                // assume a sixth of the launch
-                const long long elapsed = (long long)(now - t_role);
-                const long long need = item_ticks ? (long long)item_ticks + (long long)(item_ticks >> 3) : 0;
-                if (done >= total) go = false;
-                else if (done > 0) go = (total - done) * elapsed > (need ? need : elapsed * total / (6 * done)) * done;
-            }
-            t_claim = now;
-            if (go) {
-                int cur = __hip_atomic_load(queue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                while (cur < ready_items) {
-                    const int seen = atomicCAS(queue, cur, cur + 1);
-                    if (seen == cur) { got = cur; break; }
-                    cur = seen;
-                }
-            }
-            *lds_item = got;
-        } else {
-            *lds_item = atomicAdd(queue, 1);
-        }
-    }
+    if (tid == 0) *lds_item = atomicAdd(queue, 1);
     __syncthreads();
     const int item = __builtin_amdgcn_readfirstlane(*lds_item);
-    if (BOUNDED ? item < 0 : item >= tab.items) return;
+    if (item >= tab.items) return;
     int ji = 0;
     while (ji + 1 < tab.n && item >= tab.j[ji + 1].item0) ++ji;      // <= 40 jobs, uniform scalar scan
     const WgradJob job = tab.j[ji];
@@ -128,45 +79,21 @@ EO_DEV void wgrad_work(const Tab& tab, int* queue, float* partials, uint8_t* sme
     const bool dma_sig = has_sig && wid == AUX_SIG_WAVE, dma_emb = has_emb && wid == AUX_EMB_WAVE;
     n_dma += (dma_sig ? 1 : 0) + (dma_emb ? 1 : 0);
     // K step s = sample tile s of the slabs: one contiguous rows x 64 B region per operand.
-    // ONE descriptor per operand for the whole item (EO_WG_DESC=1): the step enters through the scalar offset of the load -- a descriptor
+    // ONE descriptor per operand for the whole item: the step enters through the scalar offset of the load -- a descriptor
     // per step is a 64-bit add and four scalar moves per operand and step (the GEMM spends 11 % of its wave cycles issuing scalar
     // instructions, profiles/r05_b_pmc_sq.csv).  Rows are clamped by the per-lane offsets, so the descriptors need no bounds; step x stride
     // stays below 2^32 inside the size guard of the training entry points (slab_blocks_addressable).
-#if EO_WG_DESC
     const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(job.a)), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(job.b)), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(has_sig ? tab.aux.a2 : job.a)), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_b2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(has_emb ? tab.aux.b2 : job.b)), 0, -1, 0x00020000);
-#endif
     auto issue = [&](int step, int slot, auto aux_c) {
         if constexpr (decltype(aux_c)::value) {      // (compiled into the Riders loops only: the other loops keep their instruction count)
-#if EO_WG_DESC
         if (dma_sig) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a2, (__attribute__((address_space(3))) void*)(lds_aux + slot * AUX_B), 16, lane * 16, (uint32_t)step * tab.aux.a2_stride, 0, 2);
         if (dma_emb) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b2, (__attribute__((address_space(3))) void*)(lds_aux + slot * AUX_B + 1024), 16, lane * 16, (uint32_t)step * tab.aux.b2_stride, 0, 2);
-#else
-        if (dma_sig) {
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(tab.aux.a2)) + (size_t)step * tab.aux.a2_stride, 0, 1024, 0x00020000);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(lds_aux + slot * AUX_B), 16, lane * 16, 0, 0, 2);
         }
-        if (dma_emb) {
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(tab.aux.b2)) + (size_t)step * tab.aux.b2_stride, 0, 1024, 0x00020000);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(lds_aux + slot * AUX_B + 1024), 16, lane * 16, 0, 0, 2);
-        }
-#endif
-        }
-        if (EO_WG_ABL & 4) return;
         uint8_t* base = smem + slot * SLOT_B + (32 * wid) * ROW_B;
-#if EO_WG_DESC
         const uint32_t so_a = (uint32_t)step * job.a_stride, so_b = (uint32_t)step * job.b_stride;
-#else
-        const uint32_t so_a = 0, so_b = 0;
-        const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(job.a)) + (size_t)step * job.a_stride, 0, job.m_rows * SEG_B, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(job.b)) + (size_t)step * job.b_stride, 0, job.n_rows * SEG_B, 0x00020000);
-#endif
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             if (on_a[j]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (__attribute__((address_space(3))) void*)(base + 16 * j * ROW_B), 16, voff_a[j], so_a, 0, 2);
@@ -225,8 +152,7 @@ EO_DEV void wgrad_work(const Tab& tab, int* queue, float* partials, uint8_t* sme
             const int slot = (s - s0) & (NS - 1);
             // this wave's share of step s has landed once at most (DEPTH-1) younger steps are outstanding; the barrier then
             // (a) publishes every wave's share and (b) retires all reads of the slot refilled next
-            if (EO_WG_ABL & 8) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_DMA * (DEPTH - 1)) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N_DMA * (DEPTH - 1)) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N_DMA * (DEPTH - 1)) : "memory");
             issue(s + DEPTH < s1 ? s + DEPTH : s1 - 1, (slot + DEPTH) & (NS - 1), aux_c);
             if (active) {
                 const uint8_t* T = smem + slot * SLOT_B;
@@ -252,8 +178,8 @@ EO_DEV void wgrad_work(const Tab& tab, int* queue, float* partials, uint8_t* sme
 #pragma unroll
                         for (int i = 0; i < 2; ++i) {
                             const U af = __builtin_bit_cast(U, u32x4{t[4 * kg + 2 * i][0], t[4 * kg + 2 * i][1], t[4 * kg + 2 * i + 1][0], t[4 * kg + 2 * i + 1][1]});
-                            acc[i][0] = EO_WG_MMA(af, bf0, acc[i][0]);
-                            if (do_bias && i == wn_idx) accb = EO_WG_MMA(af, ones, accb);
+                            acc[i][0] = P::mma(af, bf0, acc[i][0]);
+                            if (do_bias && i == wn_idx) accb = P::mma(af, ones, accb);
                         }
                     }
                 } else {
@@ -271,7 +197,7 @@ EO_DEV void wgrad_work(const Tab& tab, int* queue, float* partials, uint8_t* sme
                         if (sig_here) {      // wave-uniform
                             U as = P::zero();
                             if (r == 0) as = lds_unit<P>(X);                                                    // row 0 = d sigma_pre
-                            sr->acc = EO_WG_MMA(as, wm_idx == 0 ? bf[0] : bf[NMAX - 1], sr->acc);
+                            sr->acc = P::mma(as, wm_idx == 0 ? bf[0] : bf[NMAX - 1], sr->acc);
                             if (wid == 0) {
 #pragma unroll
                                 for (int e = 0; e < P::NE; ++e) sr->b += (float)as[e];
@@ -283,8 +209,8 @@ EO_DEV void wgrad_work(const Tab& tab, int* queue, float* partials, uint8_t* sme
                         if (i < wm) {
 #pragma unroll
                             for (int j = 0; j < NMAX; ++j)
-                                if (j < wn) acc[i][j] = EO_WG_MMA(af[i], bf[j], acc[i][j]);
-                            if (do_bias && i == wn_idx) accb = EO_WG_MMA(af[i], baux, accb);
+                                if (j < wn) acc[i][j] = P::mma(af[i], bf[j], acc[i][j]);
+                            if (do_bias && i == wn_idx) accb = P::mma(af[i], baux, accb);
                         }
                 }
                 }
@@ -344,7 +270,7 @@ EO_DEV void wgrad_work(const Tab& tab, int* queue, float* partials, uint8_t* sme
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // drain the tail prefetches before the LDS is released
 
     // ---- flush: fp32 atomics, 32 consecutive columns per half-wave instruction ----
-    if (active && !(EO_WG_ABL & 1)) {
+    if (active) {
 #pragma unroll
     for (int i = 0; i < WMAX; ++i)
         if (i < wm) {
