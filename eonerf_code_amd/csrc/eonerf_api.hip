@@ -709,10 +709,7 @@ int eonerf_set_weights(eonerf_ctx* ctx, const float* flat, void* stream) {
 
 size_t eonerf_field_workspace_bytes(const eonerf_ctx* ctx, int n_points) {
     if (!ctx || n_points < 0) return 0;
-    Carver c(nullptr);
-    PassBuffers b;
-    carve_pass(c, b, 1, round_up(std::max(n_points, 1), 256), true, false, false, ctx->bf16 ? 2 : 4);
-    return c.off + 256;
+    return carve_field(carve_cfg(ctx), nullptr, field_p_cap_of(n_points)).bytes;
 }
 
 size_t eonerf_render_workspace_bytes(const eonerf_ctx* ctx, int n_rays, int flags) {
@@ -726,9 +723,8 @@ static int field_common(eonerf_ctx* ctx, const float* flat, const float* xyz, co
     if (!ctx->weights_set) return EONERF_E_STATE;
     if (ws_bytes < eonerf_field_workspace_bytes(ctx, n)) return EONERF_E_WORKSPACE;
     drop_presample(ctx, ws);
-    p_cap = round_up(std::max(n, 1), 256);
-    Carver c(ws);
-    carve_pass(c, b, 1, p_cap, true, false, false, ctx->bf16 ? 2 : 4);
+    p_cap = field_p_cap_of(n);
+    b = carve_field(carve_cfg(ctx), ws, p_cap).b;
     HIP_TRY(eo_launch_points_to_soa(xyz, img, n, p_cap, b.px, b.py, b.pz, b.simg, b.n_pts, st));
     return run_mlp_fwd(ctx, b, flat, p_cap, full, 0, st);
 }
@@ -761,22 +757,10 @@ int eonerf_query_density(eonerf_ctx* ctx, const float* flat, const float* xyz, i
 }
 
 // ---- differentiable EONerfMLP.forward / query_density (radiance_fields/eonerf.py:141-170 under autograd) ----------------
-namespace {
-struct FieldTrainWs { PassBuffers b; float* m_bott; int* queue; size_t bytes; };
-FieldTrainWs carve_field_train(const eonerf_ctx* ctx, void* base, int p_cap, bool full) {
-    Carver c(base);
-    FieldTrainWs w;
-    carve_pass(c, w.b, 1, p_cap, full, true, true, ctx->bf16 ? 2 : 4);
-    w.m_bott = c.take<float>(BOTT_SCRATCH_F);
-    w.queue = c.take<int>(4);
-    w.bytes = c.off + 256;
-    return w;
-}
-}  // namespace
-
+// (layout: carve_field_train, eonerf_carve.h)
 size_t eonerf_field_train_workspace_bytes(const eonerf_ctx* ctx, int n_points, int density_only) {
     if (!ctx || n_points < 0) return 0;
-    return carve_field_train(ctx, nullptr, round_up(std::max(n_points, 1), 256), !density_only).bytes;
+    return carve_field_train(carve_cfg(ctx), nullptr, field_p_cap_of(n_points), !density_only).bytes;
 }
 
 int eonerf_field_forward_train(eonerf_ctx* ctx, const float* flat, const float* xyz, const float* sun, const int64_t* img, int n,
@@ -792,7 +776,7 @@ int eonerf_field_forward_train(eonerf_ctx* ctx, const float* flat, const float* 
     const int p_cap = round_up(n, 256);
     if (!slabs_addressable(ctx, (size_t)p_cap)) return EONERF_E_UNSUPPORTED;
     const bool full = !density_only;
-    FieldTrainWs w = carve_field_train(ctx, ws, p_cap, full);
+    FieldTrainWs w = carve_field_train(carve_cfg(ctx), ws, p_cap, full);
     if (ws_bytes < w.bytes) return EONERF_E_WORKSPACE;
     if (ctx->need_repack) { const int rcr = eonerf_set_weights(ctx, flat, stream); if (rcr) return rcr; }      // (after the fault fallback)
     HIP_TRY(eo_launch_points_to_soa(xyz, full ? img : nullptr, n, p_cap, w.b.px, w.b.py, w.b.pz, w.b.simg, w.b.n_pts, st));
@@ -820,7 +804,7 @@ int eonerf_field_backward(eonerf_ctx* ctx, const float* flat, const float* sun, 
     const int p_cap = round_up(n, 256);
     if (!slabs_addressable(ctx, (size_t)p_cap)) return EONERF_E_UNSUPPORTED;
     const bool full = !density_only;
-    FieldTrainWs w = carve_field_train(ctx, ws, p_cap, full);
+    FieldTrainWs w = carve_field_train(carve_cfg(ctx), ws, p_cap, full);
     if (ws_bytes < w.bytes) return EONERF_E_WORKSPACE;
     const ParamLayout& pl = ctx->pl;
     PassBuffers& b = w.b;
@@ -1339,12 +1323,34 @@ int eonerf_render_backward(eonerf_ctx* ctx, const float* flat, const float* rays
     return render_backward_impl(ctx, flat, rays, img_idx, n_rays, flags, d_out, nullptr, d_flat, ws, ws_bytes, stream);
 }
 
+// Every refusal of render_backward_impl, in its order and WITHOUT its side effects: the forward's path record is looked up, not spent
+// (PipeModeGuard erases it).  For a caller that has something to launch in front of the backward.
+static int render_backward_refusal(eonerf_ctx* ctx, const float* flat, const float* rays, const int64_t* img_idx, int n_rays, int flags,
+                                   const float* d_flat, const void* ws, size_t ws_bytes) {
+    if (!ctx || !flat || !rays || !img_idx || !d_flat || n_rays < 0 || !ws) return EONERF_E_ARG;
+    if (!(flags & EONERF_F_TRAIN) || (flags & EONERF_F_ONLY_DEPTH)) return EONERF_E_STATE;
+    if (ctx->prec == EONERF_F16X3) return EONERF_E_UNSUPPORTED;
+    if (!ctx->weights_set) return EONERF_E_STATE;
+    if (n_rays == 0) return EONERF_OK;
+    if (!rays_in_range(ctx, n_rays) || !slabs_addressable(ctx, (size_t)p_cap_of(n_rays, ctx->n_samples))) return EONERF_E_UNSUPPORTED;
+    if (ctx->pre.valid && ctx->pre.ws == ws) return EONERF_E_STATE;
+    const bool keep = ctx->pipe;      // the layout is the one of the path the forward ran on
+    const auto it = ctx->ws_pipe.find(ws);
+    if (it != ctx->ws_pipe.end()) ctx->pipe = it->second;
+    const size_t need = carve_render(ctx, nullptr, n_rays, flags).bytes;
+    ctx->pipe = keep;
+    return ws_bytes < need ? EONERF_E_WORKSPACE : EONERF_OK;
+}
+
 int eonerf_render_backward_loss(eonerf_ctx* ctx, const float* flat, const float* rays, const int64_t* img_idx,
                                 int n_rays, int flags, const float* out, const float* pixels, int kind, float* d_out_scratch, float* loss,
                                 float* d_flat, void* ws, size_t ws_bytes, void* stream) {
     if (!ctx || !out || !pixels || !loss || (kind != 0 && kind != 1) || n_rays < 1) return EONERF_E_ARG;
     if ((n_rays + 255) / 256 > LOSS_MAX_BLOCKS) {      // beyond the fused kernel's ticket sum: the two calls it replaces
         if (!d_out_scratch) return EONERF_E_ARG;
+        // (the loss kernel writes d_out_scratch and *loss: nothing is launched for a call the backward behind it will refuse)
+        const int rcr = render_backward_refusal(ctx, flat, rays, img_idx, n_rays, flags, d_flat, ws, ws_bytes);
+        if (rcr) return rcr;
         const int rc = eonerf_train_loss(ctx, out, pixels, n_rays, kind, d_out_scratch, loss, stream);
         return rc ? rc : render_backward_impl(ctx, flat, rays, img_idx, n_rays, flags, d_out_scratch, nullptr, d_flat, ws, ws_bytes, stream);
     }

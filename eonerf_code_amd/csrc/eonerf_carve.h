@@ -141,3 +141,27 @@ inline RenderWs carve_render(const CarveCfg& cfg, void* base, int n_rays, int fl
     return w;
 }
 
+// ---- EONerfMLP.forward / query_density on caller-provided points (eonerf_field_*): ONE pass over round_up(n, 256) samples ----
+inline int field_p_cap_of(int n_points) { return round_up(std::max(n_points, 1), 256); }
+
+struct FieldWs { PassBuffers b; size_t bytes; };
+// inference (eonerf_field_forward, eonerf_query_density): the layout does not depend on which outputs the call asks for
+inline FieldWs carve_field(const CarveCfg& cfg, void* base, int p_cap) {
+    Carver c(base);
+    FieldWs w;
+    carve_pass(c, w.b, 1, p_cap, true, false, false, cfg.bf16 ? 2 : 4);
+    w.bytes = c.off + 256;
+    return w;
+}
+
+struct FieldTrainWs { PassBuffers b; float* m_bott; int* queue; size_t bytes; };
+// autograd pair (eonerf_field_forward_train / eonerf_field_backward): saved slabs, input gradient, the GEMM's bottleneck factors and queue
+inline FieldTrainWs carve_field_train(const CarveCfg& cfg, void* base, int p_cap, bool full) {
+    Carver c(base);
+    FieldTrainWs w;
+    carve_pass(c, w.b, 1, p_cap, full, true, true, cfg.bf16 ? 2 : 4);
+    w.m_bott = c.take<float>(BOTT_SCRATCH_F);
+    w.queue = c.take<int>(4);
+    w.bytes = c.off + 256;
+    return w;
+}

@@ -3,7 +3,9 @@
 //     destination inside its stream, every source inside the flat buffer, no byte written twice, chunk tables consistent with the
 //     grouping the chain kernels walk;
 //   * eonerf_carve.h: the workspace layout for a set of (n_rays, flags, configuration) -- 256-byte alignment, no two buffers
-//     overlapping, everything inside the reported size, measuring pass == carving pass.
+//     overlapping, everything inside the reported size, measuring pass == carving pass; the same for the layouts of the eonerf_field_*
+//     entry points (carve_field, carve_field_train).  What the kernels then touch inside and around these spans is the device side's
+//     business: tests/test_workspace_contract.py.
 // No HIP runtime call is made (GPU sanitizers are not available on this pool; the device side is covered by the parity tests).
 #include <stdio.h>
 #include <stdlib.h>
@@ -124,6 +126,16 @@ static void add_pass(std::vector<Span>& v, const PassBuffers& b, int n_rays, siz
     add(v, "g_tb", b.g_tb, 4 * p_cap, base); add(v, "g_emb", b.g_emb, 16 * p_cap, base); add(v, "g_pos", b.g_pos, 12 * p_cap, base);
 }
 
+// 256-byte alignment, no two spans overlapping, every span inside the reported size
+static void check_spans(std::vector<Span>& v, size_t bytes) {
+    std::sort(v.begin(), v.end(), [](const Span& a, const Span& b) { return a.lo < b.lo; });
+    for (size_t i = 0; i < v.size(); ++i) {
+        CHECK(v[i].lo % 256 == 0, "%s not 256-byte aligned", v[i].name);
+        CHECK(v[i].hi <= bytes, "%s ends at %zu beyond the workspace (%zu)", v[i].name, v[i].hi, bytes);
+        if (i + 1 < v.size()) CHECK(v[i].hi <= v[i + 1].lo, "%s overlaps %s", v[i].name, v[i + 1].name);
+    }
+}
+
 static void check_carve(const CarveCfg& cfg, int n_rays, int flags) {
     const RenderWs m = carve_render(cfg, nullptr, n_rays, flags);                 // measuring pass
     // a fake, never dereferenced base: only differences of pointers are formed
@@ -152,39 +164,77 @@ static void check_carve(const CarveCfg& cfg, int n_rays, int flags) {
     add(v, "pipe_part", w.det.pipe_part, (size_t)cfg.n_pipes * PIPE_STAGES * WGRAD_PART_F * 4, base);
     add(v, "wgrad_part", w.det.wgrad_part, (size_t)WGRAD_MAX_JOBS * 48 * WGRAD_PART_F * 4, base);
     add(v, "rad_rays", w.det.rad_rays, 24 * (size_t)n_rays, base); add(v, "emb_rays", w.det.emb_rays, 16 * (size_t)n_rays, base);
+    add(v, "enc_part", w.enc_part, 4 * (size_t)cfg.enc_part_wgs * ENC_PART_F, base);
     add_pass(v, w.cam, n_rays, p_cap, !od, ab, base);
     add_pass(v, w.sun, n_rays, p_cap, false, ab, base);
-    std::sort(v.begin(), v.end(), [](const Span& a, const Span& b) { return a.lo < b.lo; });
-    for (size_t i = 0; i < v.size(); ++i) {
-        CHECK(v[i].lo % 256 == 0, "%s not 256-byte aligned", v[i].name);
-        CHECK(v[i].hi <= w.bytes, "%s ends at %zu beyond the workspace (%zu)", v[i].name, v[i].hi, w.bytes);
-        if (i + 1 < v.size()) CHECK(v[i].hi <= v[i + 1].lo, "%s overlaps %s", v[i].name, v[i + 1].name);
-    }
+    check_spans(v, w.bytes);
     const bool train = flags & EONERF_F_TRAIN;
+    CHECK(p_cap % 256 == 0 && p_cap >= 256 && p_cap >= (size_t)n_rays * (cfg.n_samples - 1), "p_cap %zu for %d rays x %d samples", p_cap, n_rays, cfg.n_samples);
     CHECK((w.cam.act != nullptr) == train && (w.g_ray != nullptr) == train, "training buffers");
+    CHECK((w.cam.g_pos != nullptr) == (train && od), "input-gradient buffer of a density-only training pass");
     CHECK((w.sun.px != nullptr) == ((flags & EONERF_F_SHADOWS) && !od), "sun pass buffers");
+    CHECK((w.enc_part != nullptr) == (train && (flags & EONERF_F_SHADOWS) && !od && cfg.pipe && cfg.enc_part_wgs > 0), "encoding partials");
+}
+
+// eonerf_field_forward / eonerf_query_density (carve_field) and eonerf_field_forward_train / eonerf_field_backward (carve_field_train)
+static void check_carve_field(const CarveCfg& cfg, int n) {
+    const size_t p_cap = (size_t)field_p_cap_of(n);
+    CHECK(p_cap % 256 == 0 && p_cap >= 256 && p_cap >= (size_t)n && p_cap < (size_t)std::max(n, 1) + 256, "field p_cap %zu for %d points", p_cap, n);
+    uint8_t* base = reinterpret_cast<uint8_t*>((uintptr_t)1 << 40);
+    const int ab = cfg.bf16 ? 2 : 4;
+    {
+        const FieldWs m = carve_field(cfg, nullptr, (int)p_cap), w = carve_field(cfg, base, (int)p_cap);
+        CHECK(w.bytes == m.bytes, "field: measuring pass %zu != carving pass %zu", m.bytes, w.bytes);
+        std::vector<Span> v;
+        add_pass(v, w.b, 1, p_cap, true, ab, base);
+        check_spans(v, w.bytes);
+        CHECK(w.b.albedo && w.b.ts && w.b.tb && !w.b.act && !w.b.grd && !w.b.masks && !w.b.g_pos, "field inference buffers");
+    }
+    for (int density_only = 0; density_only < 2; ++density_only) {
+        const bool full = !density_only;
+        const FieldTrainWs m = carve_field_train(cfg, nullptr, (int)p_cap, full), w = carve_field_train(cfg, base, (int)p_cap, full);
+        CHECK(w.bytes == m.bytes, "field train: measuring pass %zu != carving pass %zu", m.bytes, w.bytes);
+        std::vector<Span> v;
+        add_pass(v, w.b, 1, p_cap, full, ab, base);
+        add(v, "m_bott", w.m_bott, 4 * (size_t)BOTT_SCRATCH_F, base);
+        add(v, "queue", w.queue, 16, base);
+        check_spans(v, w.bytes);
+        CHECK(w.b.act && w.b.grd && w.b.masks && w.b.g_sigma && w.b.g_pos && w.m_bott && w.queue, "field training buffers");
+        CHECK((w.b.albedo != nullptr) == full && (w.b.g_albedo != nullptr) == full && (w.b.g_emb != nullptr) == full, "field head buffers");
+        CHECK(w.bytes > carve_field(cfg, nullptr, (int)p_cap).bytes || !full, "a training layout holds the inference layout and more");
+    }
 }
 
 int main() {
     for (int n_img : {1, 19, 20, 2048}) check_layout(n_img);
-    CarveCfg cfgs[5];
+    CarveCfg cfgs[7];
     cfgs[0].bf16 = false;
     cfgs[1].pipe = true; cfgs[1].n_pipes = 36;
     cfgs[2] = cfgs[1]; cfgs[2].pipe_partials = true;
     cfgs[3] = cfgs[1]; cfgs[3].deterministic = cfgs[3].pipe_partials = true;
     cfgs[4] = cfgs[1]; cfgs[4].n_pipes = 1;
+    cfgs[5] = cfgs[1]; cfgs[5].enc_part_wgs = 256;      // what a context on the pipelined path carves by default: one partial per CU (eonerf_enc_pair.hip)
+    cfgs[6] = cfgs[4]; cfgs[6].enc_part_wgs = 1;
+    // (EONERF_F_TRAIN | EONERF_F_ONLY_DEPTH: the layout of eonerf_rendering_train(depth_only) / eonerf_rendering_backward)
     const int flag_sets[] = {0, EONERF_F_SHADOWS, EONERF_F_ONLY_DEPTH, EONERF_F_TRAIN | EONERF_F_RGB_LOSS, EONERF_F_TRAIN | EONERF_F_SHADOWS,
-                             EONERF_F_SHADOWS | EONERF_F_EVAL, EONERF_F_TRAIN | EONERF_F_SHADOWS | EONERF_F_EVAL};
+                             EONERF_F_SHADOWS | EONERF_F_EVAL, EONERF_F_TRAIN | EONERF_F_SHADOWS | EONERF_F_EVAL, EONERF_F_TRAIN | EONERF_F_ONLY_DEPTH,
+                             EONERF_F_TRAIN};
     for (const CarveCfg& c : cfgs)
         for (int n_rays : {1, 37, 4096, 66050})
             for (int f : flag_sets) check_carve(c, n_rays, f);
-    // the other step sizes (eonerf_set_n_samples): 64 and 256 samples per ray
-    for (int ns : {64, 256}) {
-        CarveCfg c = cfgs[1];
-        c.n_samples = ns;
-        for (int n_rays : {1, 37, 4096, 16384})
-            for (int f : flag_sets) check_carve(c, n_rays, f);
-    }
+    // the other step sizes (eonerf_set_n_samples)
+    // (version 502 admits 2 .. 256: n_samples = 2 leaves ONE interval per ray, the smallest p_cap_of)
+    for (int ns : {2, 3, 37, 64, 255, 256})
+        for (const CarveCfg& c0 : {cfgs[0], cfgs[1], cfgs[3], cfgs[5]}) {
+            CarveCfg c = c0;
+            c.n_samples = ns;
+            for (int n_rays : {1, 37, 300, 4096, 16384})
+                for (int f : flag_sets) check_carve(c, n_rays, f);
+        }
+    CHECK(p_cap_of(1, 2) == 256 && p_cap_of(256, 2) == 256 && p_cap_of(257, 2) == 512 && p_cap_of(0, 2) == 256 && p_cap_of(300, 255) == 76288, "p_cap_of corners");
+    // the field entry points: one pass over round_up(n, 256) points, whatever the render configuration of the context
+    for (const CarveCfg& c : {cfgs[0], cfgs[1], cfgs[3], cfgs[5]})
+        for (int n : {0, 1, 255, 256, 257, 1000, 2097152}) check_carve_field(c, n);
     CHECK(slab_blocks_addressable(true, (size_t)p_cap_of(66050, 128)) && !slab_blocks_addressable(true, (size_t)p_cap_of(66051, 128)), "bf16 size guard");
     CHECK(slab_blocks_addressable(false, (size_t)p_cap_of(33024, 128)) && !slab_blocks_addressable(false, (size_t)p_cap_of(33025, 128)), "fp32 size guard");
     if (g_fail) { fprintf(stderr, "%d check(s) failed\n", g_fail); return 1; }
