@@ -1,5 +1,5 @@
 // Workspace carving of the C ABI (eonerf_render_workspace_bytes / eonerf_render_forward / _backward; eonerf_field_*): plain host code,
-// no HIP runtime calls -- shared by eonerf_api.hip and the host-only sanitizer test (tests/host/host_checks.cpp, built for the CPU
+// no HIP runtime calls -- shared by the entry points (eonerf_field.hip, eonerf_render.hip) and the host-only sanitizer test (tests/host/host_checks.cpp, built for the CPU
 // under the address + undefined-behaviour sanitizers).  The caller (PyTorch) owns the workspace; these functions only lay it out.
 #pragma once
 #include <stdint.h>
@@ -139,6 +139,15 @@ inline RenderWs carve_render(const CarveCfg& cfg, void* base, int n_rays, int fl
     if (shadows && !od) carve_pass(c, w.sun, n_rays, p_cap, false, train, true, ab); else memset(&w.sun, 0, sizeof(w.sun));
     w.bytes = c.off + 256;
     return w;
+}
+
+// Everything a pipelined backward call needs zeroed, as ONE span: [bottleneck factors | GEMM work queue | the PIPE_LAUNCHES sync blocks].
+// Cleared by the call's first kernel (ShadeBwdArgs::zero_base) or by the memset in front of its first pipelined launch
+struct ZeroSpan { uint8_t* base; size_t bytes; };
+inline ZeroSpan backward_zero_span(const RenderWs& w) {
+    uint8_t* lo = reinterpret_cast<uint8_t*>(w.m_bott);
+    uint8_t* hi = reinterpret_cast<uint8_t*>(w.pipe.sync) + PIPE_LAUNCHES * w.pipe.sync_bytes;
+    return ZeroSpan{lo, (size_t)(hi - lo)};
 }
 
 // ---- EONerfMLP.forward / query_density on caller-provided points (eonerf_field_*): ONE pass over round_up(n, 256) samples ----

@@ -1,4 +1,4 @@
-// Host<->kernel argument blocks and layout constants shared by the launchers (eonerf_api.cpp) and the kernels.
+// Host<->kernel argument blocks and layout constants shared by the entry points (eonerf_ctx.hip, eonerf_field.hip, eonerf_render.hip) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -186,7 +186,7 @@ bool eo_bwd_pipe_fits_a_cu();
 hipError_t eo_launch_mlp_fwd(const MlpFwdArgs& a, int prec, bool full, int mode, int grid, hipStream_t st);      // prec: 0 fp32, 1 bf16, 2 fp16 x 3 (inference)
 // pipe: 0 = the whole dX chain; 1 = stop at dY_7 (the trunk is pipelined)
 hipError_t eo_launch_mlp_bwd(const MlpBwdArgs& a, bool bf16, bool full, bool input_grad, bool transient, int grid, hipStream_t st, int pipe = 0);
-constexpr int WGRAD_MAX_JOBS = 32;     // <= 31 used (fp32 chain + GEMM path, full model); the table must fit the 4-KiB kernel-argument segment
+constexpr int WGRAD_MAX_JOBS = 32;     // 27 used at most (chain + GEMM path, full model without riders + a density pass: wgrad_plan refuses a 33rd); the table must fit the 4-KiB kernel-argument segment
 static_assert(sizeof(WgradJob) * WGRAD_MAX_JOBS + 8 + 64 <= 4096, "job table exceeds the kernel-argument segment");
 // Riders of ONE job (the bottleneck-factor job [dY_A1; dY_T1] x X_8 of the camera pass): two tiny products whose big operand that job
 // streams anyway, so that nothing reads it a second time --

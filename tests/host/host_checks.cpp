@@ -6,6 +6,9 @@
 //     overlapping, everything inside the reported size, measuring pass == carving pass; the same for the layouts of the eonerf_field_*
 //     entry points (carve_field, carve_field_train).  What the kernels then touch inside and around these spans is the device side's
 //     business: tests/test_workspace_contract.py.
+//   * eonerf_wgrad_plan.h: the job table and slice plan of the weight-gradient GEMM launch for every reachable combination of precision,
+//     backward path, pass set and switches -- the table fits, the items are a running sum that fits deterministic mode's partial buffer,
+//     every operand stays inside the slab block it starts in, the wave grid covers the product, the riders sit on the right job.
 // No HIP runtime call is made (GPU sanitizers are not available on this pool; the device side is covered by the parity tests).
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,6 +18,7 @@
 
 #include "../../eonerf_code_amd/csrc/eonerf_pack.h"
 #include "../../eonerf_code_amd/csrc/eonerf_carve.h"
+#include "../../eonerf_code_amd/csrc/eonerf_wgrad_plan.h"
 
 static int g_fail = 0;
 #define CHECK(c, ...) do { if (!(c)) { ++g_fail; fprintf(stderr, "FAIL %s:%d: %s -- ", __FILE__, __LINE__, #c); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } } while (0)
@@ -205,6 +209,106 @@ static void check_carve_field(const CarveCfg& cfg, int n) {
     }
 }
 
+// ---- weight-gradient job planner (eonerf_wgrad_plan.h) ----
+// the slab block an operand address starts in and its first row, decoded from the block-major layout ([block][sample tile][row][SEG_B],
+// eonerf_common.h) independently of the planner; needs n_tiles >= the largest block (256 rows)
+template <class Map> static bool operand_rows(const void* p, const void* slab, size_t n_tiles, int slab_rows, int rows, uint32_t stride, const char* what) {
+    const size_t off = (size_t)(reinterpret_cast<const uint8_t*>(p) - reinterpret_cast<const uint8_t*>(slab));
+    CHECK(p && slab && off % SEG_B == 0, "%s: operand not on a segment", what);
+    const size_t q = off / SEG_B;
+    for (int r = 0; r < slab_rows; r += Map::block(r).r) {
+        const SlabBlk blk = Map::block(r);
+        if (q < (size_t)blk.s * n_tiles || q >= (size_t)blk.s * n_tiles + blk.r) continue;
+        const int row0 = blk.s + (int)(q - (size_t)blk.s * n_tiles);
+        CHECK(row0 + rows <= blk.s + blk.r && blk.s + blk.r <= slab_rows, "%s: rows %d..%d leave block [%d, %d) of a %d-row slab", what, row0, row0 + rows, blk.s, blk.s + blk.r, slab_rows);
+        CHECK(stride == (uint32_t)(blk.r * SEG_B), "%s: tile stride %u of a %d-row block", what, stride, blk.r);
+        return true;
+    }
+    CHECK(false, "%s: operand at segment %zu is in no block of the slab", what, q);
+    return false;
+}
+
+struct PlanCase { bool bf16, pipelined; int state; bool riders, det, enc_done; int n_cu; };      // state: 0 full + transient, 1 full rgb, 2 density only, 3 full + sun
+static int check_wgrad_plan(const PlanCase& pc, const ParamLayout& pl) {
+    char tag[160];
+    snprintf(tag, sizeof(tag), "plan %s %s state %d riders %d det %d enc_done %d n_cu %d", pc.bf16 ? "bf16" : "fp32", pc.pipelined ? "pipe" : "gemm", pc.state,
+             pc.riders, pc.det, pc.enc_done, pc.n_cu);
+    CarveCfg cfg;
+    cfg.bf16 = pc.bf16; cfg.pipe = pc.pipelined; cfg.n_pipes = pc.n_cu / PIPE_STAGES; cfg.deterministic = cfg.pipe_partials = pc.det;
+    cfg.enc_part_wgs = pc.enc_done ? pc.n_cu : 0;
+    const int n_rays = 128, flags = EONERF_F_TRAIN | (pc.state == 3 ? EONERF_F_SHADOWS : 0) | (pc.state == 2 ? EONERF_F_ONLY_DEPTH : 0);
+    // fake, never dereferenced bases: the planner only forms addresses
+    uint8_t* base = reinterpret_cast<uint8_t*>((uintptr_t)1 << 40);
+    float* d_flat = reinterpret_cast<float*>((uintptr_t)1 << 41);
+    const int* colmap = reinterpret_cast<const int*>((uintptr_t)1 << 42);
+    const RenderWs w = carve_render(cfg, base, n_rays, flags);
+    const int p_cap = p_cap_of(n_rays, cfg.n_samples);
+    const size_t n_tiles = (size_t)p_cap / (pc.bf16 ? 32 : 16);
+    CHECK(n_tiles >= 256, "%s: too few sample tiles to decode a block", tag);
+    const PassBuffers* full = pc.state == 2 ? nullptr : &w.cam;
+    const PassBuffers* dens = pc.state == 2 ? &w.cam : pc.state == 3 ? &w.sun : nullptr;
+    WgradPlanOpts o;      // as camera_backward sets them (eonerf_render.hip); the chain + GEMM cases are eonerf_field_backward's as well
+    o.transient = pc.state != 1;
+    o.full_trunk_done = pc.pipelined; o.dens_trunk_done = pc.pipelined && dens; o.dens_enc_done = pc.enc_done; o.zeroed = pc.pipelined;
+    o.riders = pc.riders; o.deterministic = pc.det;
+    WgradJobTable tab;
+    memset(&tab, 0xff, sizeof(tab));
+    const bool ok = wgrad_plan(tab, full, dens, pc.bf16, p_cap, pc.n_cu, d_flat, pl, colmap, w.m_bott, o);
+    CHECK(ok && tab.n >= 1 && tab.n <= WGRAD_MAX_JOBS, "%s: %d jobs", tag, tab.n);
+    if (!ok || tab.n < 1 || tab.n > WGRAD_MAX_JOBS) return 0;
+    int items = 0, bott_job = -1;
+    for (int k = 0; k < tab.n; ++k) {
+        const WgradJob& j = tab.j[k];
+        CHECK(j.item0 == items && j.slices >= 1, "%s job %d: item0 %d after %d items, %d slices", tag, k, j.item0, items, j.slices);
+        if (pc.det) CHECK(j.slices <= 48, "%s job %d: %d slices in deterministic mode", tag, k, j.slices);
+        items += j.slices;
+        CHECK(j.gm * j.wm * 32 >= j.m_rows && j.gn * j.wn * 32 >= j.n_rows && j.m_rows >= 1 && j.n_rows >= 1, "%s job %d: (%d x %d x 32) x (%d x %d x 32) waves for %d x %d", tag, k, j.gm, j.wm, j.gn, j.wn, j.m_rows, j.n_rows);
+        const bool of_full = full && j.n_pts == full->n_pts;
+        CHECK(of_full || (dens && j.n_pts == dens->n_pts), "%s job %d: sample count of no pass", tag, k);
+        const PassBuffers& b = of_full ? *full : *dens;
+        operand_rows<GrdMap>(j.a, b.grd, n_tiles, of_full ? GRD_ROWS_FULL : GRD_ROWS_DENSITY, j.m_rows, j.a_stride, tag);
+        operand_rows<ActMap>(j.b, b.act, n_tiles, of_full ? ACT_ROWS_FULL : ACT_ROWS_DENSITY, j.n_rows, j.b_stride, tag);
+        const bool to_scratch = j.dw >= w.m_bott && j.dw < w.m_bott + BOTT_SCRATCH_F;
+        CHECK(to_scratch || (j.dw >= d_flat && j.dw + (size_t)(j.split - 1) * j.dw_ld < d_flat + pl.total), "%s job %d: destination outside the gradient buffer", tag, k);
+        CHECK((j.split == j.m_rows) == (j.dw2 == nullptr) && j.split >= 1 && j.split <= j.m_rows, "%s job %d: split %d of %d rows", tag, k, j.split, j.m_rows);
+        CHECK(j.a_units == ((pc.pipelined && j.n_rows == 64) ? 1 : 0), "%s job %d: a_units %d", tag, k, j.a_units);      // only dY_0 / dY_5 are left in unit order
+        if (to_scratch) { CHECK(bott_job < 0 && j.dw == w.m_bott, "%s: two bottleneck-factor jobs", tag); bott_job = k; }
+    }
+    CHECK(tab.items == items, "%s: %d items, slices sum to %d", tag, tab.items, items);
+    if (pc.det) CHECK(tab.items <= WGRAD_MAX_JOBS * 48, "%s: %d items beyond the partial buffer", tag, tab.items);
+    CHECK((bott_job >= 0) == (full != nullptr), "%s: bottleneck-factor job %d", tag, bott_job);
+    const bool riders = full && pc.riders && !pc.det;
+    CHECK(tab.aux.job == (riders ? bott_job : -1), "%s: riders on job %d, bottleneck-factor job %d", tag, tab.aux.job, bott_job);
+    if (riders) {
+        operand_rows<GrdMap>(tab.aux.a2, full->grd, n_tiles, GRD_ROWS_FULL, 1, tab.aux.a2_stride, tag);
+        CHECK((tab.aux.b2 != nullptr) == o.transient, "%s: embedding rider", tag);
+        if (tab.aux.b2) operand_rows<ActMap>(tab.aux.b2, full->act, n_tiles, ACT_ROWS_FULL, 4, tab.aux.b2_stride, tag);
+    }
+    return tab.n;
+}
+
+static void check_wgrad_plans() {
+    ParamLayout pl;
+    pl.build(20);
+    int most = 0;
+    for (int bf16 = 0; bf16 < 2; ++bf16)
+        for (int pipelined = 0; pipelined <= bf16; ++pipelined)          // the pipelined backward is a bf16 path
+            for (int state = 0; state < 4; ++state)
+                for (int riders = 0; riders < 2; ++riders)
+                    for (int det = 0; det < 2; ++det)
+                        for (int enc_done = 0; enc_done <= (pipelined && state == 3 && !det ? 1 : 0); ++enc_done)      // eonerf_enc_pair.hip: shadow pass, pipelined, atomic mode
+                            for (int n_cu : {256, 64, 7}) {
+                                const PlanCase pc{bf16 != 0, pipelined != 0, state, riders != 0, det != 0, enc_done != 0, n_cu};
+                                const int n = check_wgrad_plan(pc, pl);
+                                most = std::max(most, n);
+                                // anchors: the default bf16 states of the training step
+                                if (bf16 && pipelined && riders && !det && state == 1) CHECK(n == 4, "rgb state plans %d jobs", n);
+                                if (bf16 && pipelined && riders && !det && state == 3 && enc_done) CHECK(n == 9, "full step plans %d jobs", n);
+                            }
+    CHECK(most <= 31, "largest table: %d jobs", most);
+    printf("wgrad plans: at most %d jobs\n", most);
+}
+
 int main() {
     for (int n_img : {1, 19, 20, 2048}) check_layout(n_img);
     CarveCfg cfgs[7];
@@ -237,6 +341,7 @@ int main() {
         for (int n : {0, 1, 255, 256, 257, 1000, 2097152}) check_carve_field(c, n);
     CHECK(slab_blocks_addressable(true, (size_t)p_cap_of(66050, 128)) && !slab_blocks_addressable(true, (size_t)p_cap_of(66051, 128)), "bf16 size guard");
     CHECK(slab_blocks_addressable(false, (size_t)p_cap_of(33024, 128)) && !slab_blocks_addressable(false, (size_t)p_cap_of(33025, 128)), "fp32 size guard");
+    check_wgrad_plans();
     if (g_fail) { fprintf(stderr, "%d check(s) failed\n", g_fail); return 1; }
     printf("host checks ok\n");
     return 0;
