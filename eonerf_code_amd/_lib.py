@@ -25,6 +25,10 @@ SYMBOLS = ["eonerf_version", "eonerf_strerror", "eonerf_create", "eonerf_destroy
            "eonerf_field_backward", "eonerf_set_noise_seed", "eonerf_render_status", "eonerf_device_status", "eonerf_grad_floats",
            "eonerf_grad_seal", "eonerf_profile_name", "eonerf_adam_step_zero_grad", "eonerf_rendering_train", "eonerf_rendering_backward", "eonerf_clock_probe", "eonerf_range_status", "eonerf_set_n_samples", "eonerf_render_backward_loss",
            "eonerf_presample", "eonerf_presample_cancel", "eonerf_grad_early_floats", "eonerf_set_exchange_event"]
+# include/eonerf_dsm.h: the stateless DSM evaluation group of the same library
+DSM_SYMBOLS = ["eonerf_dsm_version", "eonerf_nadir_rays", "eonerf_dsm_rasterize", "eonerf_dsm_mask_water",
+               "eonerf_dsm_register_workspace_bytes", "eonerf_dsm_register_levels", "eonerf_dsm_register_level",
+               "eonerf_dsm_register", "eonerf_dsm_mae_workspace_bytes", "eonerf_dsm_mae"]
 
 
 class EonerfRpc(C.Structure):
@@ -45,6 +49,7 @@ def build(verbose=False):
     import hashlib
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h")) or f == "Makefile")
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_hip.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_dsm.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -138,7 +143,19 @@ def lib():
     L.eonerf_clock_probe.argtypes = [vp, vp, vp]
     L.eonerf_profile_name.restype = C.c_char_p
     L.eonerf_profile_name.argtypes = [i]
-    for name in SYMBOLS:
+    d3 = C.POINTER(C.c_double)
+    L.eonerf_dsm_version.restype = i
+    L.eonerf_nadir_rays.argtypes = [i, i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, d3, C.c_double, C.c_double, vp, vp]
+    L.eonerf_dsm_rasterize.argtypes = [vp, i, vp, C.c_long, d3, d3, C.c_double, C.c_double, i, i, C.c_double, vp, vp, vp, vp]
+    L.eonerf_dsm_mask_water.argtypes = [vp, i, i, vp, i, i, vp]
+    L.eonerf_dsm_register_workspace_bytes.restype = sz
+    L.eonerf_dsm_register_workspace_bytes.argtypes = [i, i, i, i]
+    L.eonerf_dsm_register_levels.argtypes = [i, i]
+    L.eonerf_dsm_register_level.argtypes = [i, i, i, i, i, C.POINTER(i), C.POINTER(sz)]
+    L.eonerf_dsm_register.argtypes = [vp, i, i, vp, i, i, i, vp, vp, sz, vp]
+    L.eonerf_dsm_mae_workspace_bytes.restype = sz
+    L.eonerf_dsm_mae.argtypes = [vp, i, i, vp, i, i, vp, i, i, vp, vp, vp, vp, sz, vp]
+    for name in SYMBOLS + DSM_SYMBOLS:
         getattr(L, name)
     _lib = L
     return L

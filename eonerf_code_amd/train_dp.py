@@ -8,6 +8,11 @@
 datasets/satellite.py:406-481 builds it (eonerf_code_amd.datasets.satellite.generate_rays produces the rays on the
 GPU); without it a synthetic JAX_068-like table is used.  Same schedule as the reference: seed 42, Adam lr 5e-4,
 StepLR gamma 0.9 per epoch, MSE for epoch < 2 then the uncertainty loss with the shadow pass on.
+
+`--gt_dsm` is a torch file {"dsm": [H,W] fp32 lidar DSM, "roi": [xoff, yoff, size, res], "scene_offset": [3], "scene_scale": [3],
+optional "water": [H,W] uint8, optional "sun": [elevation_deg, azimuth_deg] of the nadir camera's sun direction}.  With it, after
+every epoch (val_freq, train_eonerf.py:194) every rank checks its device status and rank 0 renders the nadir DSM, registers it on
+the ground truth and prints val/mae -- all on the GPU (eonerf_code_amd.dsm.evaluate_dsm).  Without it nothing changes.
 """
 import argparse
 import os
@@ -30,6 +35,8 @@ def main():
     ap.add_argument("--synthetic_rays", type=int, default=1 << 20)
     ap.add_argument("--check_every", type=int, default=1000, help="steps between host syncs (loss print + device status on every rank)")
     ap.add_argument("--dump_params", default=None, help="write the final flat parameters of every rank to <path>.rank<r>")
+    ap.add_argument("--gt_dsm", default=None, help="torch file with the lidar DSM, its ROI and the scene normalisation: DSM MAE after every epoch")
+    ap.add_argument("--val_chunk", type=int, default=5120, help="rays per chunk of the validation render")
     args = ap.parse_args()
 
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -65,6 +72,15 @@ def main():
     trainer = FusedTrainer(field, lr=args.lr, max_rays=args.batch_size, keep_message=False, n_samples=args.n_samples)
     trainer.set_noise_seed(42 + 1000003 * rank)                              # per-rank jitter stream
     steps_per_epoch = max(1, table.steps_per_epoch(args.batch_size))
+    gt = None
+    if args.gt_dsm:
+        gt = torch.load(args.gt_dsm, map_location="cpu")
+        for key in ("dsm", "roi", "scene_offset", "scene_scale"):
+            if key not in gt:
+                raise SystemExit(f"--gt_dsm {args.gt_dsm}: missing entry '{key}'")
+        if rank == 0:
+            gt["dsm"] = gt["dsm"].to(dev, torch.float32)
+            gt["water"] = gt["water"].to(dev, torch.uint8) if gt.get("water") is not None else None
     step, tic = 0, time.time()
     for epoch in range(10 ** 7):
         for i in range(steps_per_epoch):
@@ -97,6 +113,15 @@ def main():
                     torch.distributed.destroy_process_group()
                 return
             step += 1
+        if gt is not None:                                                  # val_freq = one epoch (:194)
+            trainer.check_device_status()                                   # on every rank: no validation of weights a fault has frozen
+            if rank == 0:
+                from .dsm import evaluate_dsm
+                sun = [float(x) for x in gt.get("sun", (0.0, 0.0))]
+                mae = evaluate_dsm(field, gt["dsm"], [float(x) for x in gt["roi"]], gt["scene_offset"], gt["scene_scale"], sun,
+                                   chunk=args.val_chunk, water=gt["water"])
+                mae, n_valid = mae.tolist()                                 # the validation's one read-back
+                print(f"epoch={epoch} | elapsed_time={time.time() - tic:.2f}s | step={step} | val/mae={mae:.4f} | val/cells={int(n_valid)}", flush=True)
         trainer.set_lr(trainer.lr * 0.9)                                    # StepLR(step_size=1, gamma=0.9), :64,304
 
 

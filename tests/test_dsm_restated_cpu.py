@@ -1,0 +1,112 @@
+"""CPU: the numpy restatement of the DSM evaluation contract (tests/dsm_restated.py) reproduces what the reference's own code
+recorded in g11_nadir.npz / g12_dsmr.npz (tests/golden/make_golden_dsm.py), and the library exports include/eonerf_dsm.h."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import REPO, load_golden
+import dsm_restated as R
+
+
+def ulp32(x):
+    return np.spacing(np.abs(np.asarray(x, dtype=np.float32)))
+
+
+def test_dsm_header_symbols_exported():
+    from eonerf_code_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    hdr = open(os.path.join(REPO, "include", "eonerf_dsm.h")).read()
+    declared = set(re.findall(r"^(?:int|size_t)\s+(eonerf_[a-z_]+)\s*\(", hdr, flags=re.M))
+    assert declared == set(_lib.DSM_SYMBOLS) and len(declared) == 10
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    for name in declared:
+        assert hasattr(L, name), name
+    L.eonerf_dsm_version.restype = ctypes.c_int
+    assert L.eonerf_dsm_version() == 1
+    assert not set(_lib.DSM_SYMBOLS) & set(_lib.SYMBOLS)
+
+
+def test_register_layout_queries():
+    """Host-side queries need no GPU: levels follow min(h, w) > 100 of ref, sizes ceil(n / 2), offsets inside the workspace."""
+    from eonerf_code_amd import _lib
+    L = _lib.lib()
+    assert L.eonerf_dsm_register_levels(100, 400) == 1 and L.eonerf_dsm_register_levels(101, 101) == 2
+    assert L.eonerf_dsm_register_levels(512, 512) == 4          # 512, 256, 128, 64
+    dims, offs = (ctypes.c_int * 4)(), (ctypes.c_size_t * 4)()
+    assert L.eonerf_dsm_register_level(118, 105, 64, 76, 1, dims, offs) == 0
+    assert list(dims) == [59, 53, 32, 38]
+    total = L.eonerf_dsm_register_workspace_bytes(118, 105, 64, 76)
+    assert all(o % 16 == 0 for o in offs) and offs[3] + 32 * 38 * 8 <= total
+    assert L.eonerf_dsm_register_level(118, 105, 64, 76, 2, dims, offs) == -1
+    assert L.eonerf_dsm_register_workspace_bytes(0, 5, 5, 5) == 0
+
+
+def test_restated_nadir_rays_match_the_reference():
+    g = load_golden("g11_nadir")
+    scale = g["scene_scale"]
+    for h, w in g["sizes"]:
+        for k, (sel, saz) in enumerate(g["suns"]):
+            want = g[f"nadir.{h}x{w}.sun{k}"]
+            got = R.nadir_rays(h, w, 2.0, 0.0, 0.0, 0.0, 2.5, scale, sel, saz)
+            assert got.shape == want.shape
+            assert (np.abs(got.astype(np.float64) - want) <= ulp32(want)).all()
+            assert (got[:, 6] == 0).all() and (got[:, 7] == 2.5).all()
+        want = g[f"oblique.{h}x{w}"]
+        got = R.nadir_rays(h, w, 2.0, 10.0, 135.0, 0.0, 2.5, scale, 0.0, 0.0)[:, :8]
+        assert (np.abs(got.astype(np.float64) - want) <= ulp32(want)).all()
+
+
+@pytest.mark.parametrize("tag", ["a", "b", "bw"])
+def test_restated_registration_and_mae_match_the_reference(tag):
+    g = load_golden("g12_dsmr")
+    gt = g[("b" if tag == "bw" else tag) + ".gt"]
+    sec = g[("b" if tag == "bw" else tag) + ".pred"]
+    water = g["bw.water"] if tag == "bw" else None
+    if water is not None:
+        sec = R.mask_water(sec, water)
+    r = R.register(gt, sec, scaling=False)
+    assert len(r["levels"]) == int(g[f"{tag}.n_levels"])
+    for k, lv in enumerate(r["levels"]):
+        assert tuple(lv["centre"]) == tuple(g[f"{tag}.level{k}.centre"])
+        assert tuple(lv["shift"]) == tuple(g[f"{tag}.level{k}.shift"])
+        np.testing.assert_allclose(lv["scores"], g[f"{tag}.level{k}.scores"], rtol=0, atol=1e-9, equal_nan=True)
+        if k:
+            np.testing.assert_array_equal(lv["ref"], g[f"{tag}.level{k}.ref"])
+            np.testing.assert_array_equal(lv["sec"], g[f"{tag}.level{k}.sec"])
+    np.testing.assert_allclose(r["transform"], g[f"{tag}.transform"], rtol=0, atol=1e-9)
+    np.testing.assert_allclose(R.register(gt, sec, scaling=True)["transform"], g[f"{tag}.transform_scaling"], rtol=0, atol=1e-9)
+    np.testing.assert_allclose(R.mean_std(gt, sec, *r["transform"][:2]), g[f"{tag}.mean_std"], rtol=0, atol=1e-9)
+    err, mae, n = R.dsm_error(gt, sec, g[f"{tag}.transform"])
+    np.testing.assert_array_equal(np.isnan(err), np.isnan(g[f"{tag}.err"]))
+    np.testing.assert_array_equal(err, g[f"{tag}.err"])
+    assert n == int(g[f"{tag}.n_valid"]) and abs(mae - float(g[f"{tag}.mae"])) <= 1e-6
+
+
+def test_downsample_quirk_is_the_shifted_window():
+    g = load_golden("g12_dsmr")
+    u, su = g["a.gt"].astype(np.float64), g["a.level1.ref"]
+    assert su.shape == (59, 53)
+    assert su[3, 4] == u[7:9, 9:11].mean() and su[3, 4] != u[6:8, 8:10].mean()
+    assert su[58, 52] == u[117, 104]                      # odd sizes: the last cell is the last pixel alone
+
+
+def test_restated_rasteriser_contract_by_hand():
+    # one ray straight down onto (east 2.25, north 7.75) at altitude 11 on a 4 x 3 grid of 1 m cells with its corner at (0, 10)
+    rays = np.array([[0.25, 0.75, 1.0, 0.0, 0.0, -1.0]], dtype=np.float32)
+    depth = np.array([0.5], dtype=np.float32)
+    dsm, count = R.rasterize(rays, depth, (1.0, 1.0, 2.0), (2.0, 7.0, 10.0), 0.0, 10.0, 4, 3, 1.0)
+    want = np.full((3, 4), np.nan)
+    want[1:3, 1:4] = 11.0                                 # cell (j, i) = (2, 2): rows 1..3 clipped to 1..2, columns 1..3
+    np.testing.assert_array_equal(dsm, want)
+    # a second ray into the same cell averages; depth < 0, NaN and inf are dropped; a negative northing moves by 10e6
+    rays = np.repeat(rays, 5, axis=0)
+    depth = np.array([0.5, 0.0, -0.1, np.nan, np.inf], dtype=np.float32)
+    dsm, count = R.rasterize(rays, depth, (1.0, 1.0, 2.0), (2.0, 7.0, 10.0), 0.0, 10.0, 4, 3, 1.0)
+    assert count[2, 2] == 2 and dsm[2, 2] == 11.5
+    dsm2, _ = R.rasterize(rays, depth, (1.0, 1.0, 2.0), (2.0, 7.0 - 10e6, 10.0), 0.0, 10.0, 4, 3, 1.0)
+    np.testing.assert_array_equal(np.isnan(dsm2), np.isnan(dsm))
+    assert R.grid_from_roi([100.0, 200.0, 48, 0.5]) == (100.0, 224.0, 48, 48, 0.5)
