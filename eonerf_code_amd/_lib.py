@@ -29,6 +29,8 @@ SYMBOLS = ["eonerf_version", "eonerf_strerror", "eonerf_create", "eonerf_destroy
 DSM_SYMBOLS = ["eonerf_dsm_version", "eonerf_nadir_rays", "eonerf_dsm_rasterize", "eonerf_dsm_mask_water",
                "eonerf_dsm_register_workspace_bytes", "eonerf_dsm_register_levels", "eonerf_dsm_register_level",
                "eonerf_dsm_register", "eonerf_dsm_mae_workspace_bytes", "eonerf_dsm_mae"]
+# include/eonerf_prior.h: the stateless depth-prior group (initial DSM -> per-ray depth / confidence)
+PRIOR_SYMBOLS = ["eonerf_prior_version", "eonerf_prior_workspace_bytes", "eonerf_prior_reproject"]
 
 
 class EonerfRpc(C.Structure):
@@ -50,6 +52,7 @@ def build(verbose=False):
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h")) or f == "Makefile")
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_hip.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_dsm.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_prior.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -155,7 +158,11 @@ def lib():
     L.eonerf_dsm_register.argtypes = [vp, i, i, vp, i, i, i, vp, vp, sz, vp]
     L.eonerf_dsm_mae_workspace_bytes.restype = sz
     L.eonerf_dsm_mae.argtypes = [vp, i, i, vp, i, i, vp, i, i, vp, vp, vp, vp, sz, vp]
-    for name in SYMBOLS + DSM_SYMBOLS:
+    L.eonerf_prior_version.restype = i
+    L.eonerf_prior_workspace_bytes.restype = sz
+    L.eonerf_prior_workspace_bytes.argtypes = [i, i]
+    L.eonerf_prior_reproject.argtypes = [vp, vp, i, i, d3, C.POINTER(EonerfRpc), i, i, i, i, vp, i, vp, i, fp, fp, vp, vp, sz, vp]
+    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS:
         getattr(L, name)
     _lib = L
     return L

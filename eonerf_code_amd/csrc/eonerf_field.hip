@@ -4,6 +4,7 @@
 
 #include "eonerf_ctx.h"
 #include "eonerf_raygen.h"
+#include "eonerf_rpc_dev.h"
 
 extern "C" {
 
@@ -133,19 +134,7 @@ int eonerf_generate_rays(const eonerf_rpc* rpc, const double* cols, const double
     static_assert(sizeof(eonerf_rpc) == sizeof(RpcModel), "RPC struct mismatch");
     RayGenArgs a;
     memcpy(&a.rpc, rpc, sizeof(RpcModel));
-    // WGS84, Krueger series coefficients (Karney 2011, eq. 35) -- what PROJ's etmerc evaluates
-    const double f = 1.0 / 298.257223563, nn = f / (2.0 - f);
-    const double n2 = nn * nn, n3 = n2 * nn, n4 = n3 * nn, n5 = n4 * nn, n6 = n5 * nn;
-    a.utm.lon0_deg = utm_zone * 6.0 - 183.0;
-    a.utm.e = sqrt(f * (2.0 - f));
-    a.utm.k0A = 0.9996 * 6378137.0 / (1.0 + nn) * (1.0 + n2 / 4 + n4 / 64 + n6 / 256);
-    a.utm.false_north = south ? 10000000.0 : 0.0;
-    a.utm.alpha[0] = nn / 2 - 2 * n2 / 3 + 5 * n3 / 16 + 41 * n4 / 180 - 127 * n5 / 288 + 7891 * n6 / 37800;
-    a.utm.alpha[1] = 13 * n2 / 48 - 3 * n3 / 5 + 557 * n4 / 1440 + 281 * n5 / 630 - 1983433 * n6 / 1935360;
-    a.utm.alpha[2] = 61 * n3 / 240 - 103 * n4 / 140 + 15061 * n5 / 26880 + 167603 * n6 / 181440;
-    a.utm.alpha[3] = 49561 * n4 / 161280 - 179 * n5 / 168 + 6601661 * n6 / 7257600;
-    a.utm.alpha[4] = 34729 * n5 / 80640 - 3418889 * n6 / 1995840;
-    a.utm.alpha[5] = 212378941 * n6 / 319334400;
+    a.utm = eo_utm_params(utm_zone, south);
     a.cols = cols; a.rows = rows; a.n = n; a.width = width; a.min_alt = min_alt; a.max_alt = max_alt;
     // get_sun_dirs(90 - elevation, azimuth) -> get_dir_vec_from_el_az (datasets/satellite.py:457,57-63)
     const double d2r = 0.017453292519943295;

@@ -7,27 +7,9 @@
 // Everything is fp64 (one thread per pixel) except the reference's own fp32 cast (datasets/satellite.py:119-120).
 #include <hip/hip_runtime.h>
 #include "eonerf_raygen.h"
+#include "eonerf_rpc_dev.h"
 
 namespace {
-
-__device__ __forceinline__ double poly20(const double* p, double x, double y, double z) {   // sat_utils.py:437-450
-    double out = 0;
-    out += p[0];
-    out += p[1] * y + p[2] * x + p[3] * z;
-    out += p[4] * y * x + p[5] * y * z + p[6] * x * z;
-    out += p[7] * y * y + p[8] * x * x + p[9] * z * z;
-    out += p[10] * x * y * z;
-    out += p[11] * y * y * y;
-    out += p[12] * y * x * x + p[13] * y * z * z + p[14] * y * y * x;
-    out += p[15] * x * x * x;
-    out += p[16] * x * z * z + p[17] * y * y * z + p[18] * x * x * z;
-    out += p[19] * z * z * z;
-    return out;
-}
-__device__ __forceinline__ void project_n(const RpcModel& r, double nlat, double nlon, double nalt, double& x, double& y) {
-    x = poly20(r.col_num, nlat, nlon, nalt) / poly20(r.col_den, nlat, nlon, nalt);
-    y = poly20(r.row_num, nlat, nlon, nalt) / poly20(r.row_den, nlat, nlon, nalt);
-}
 
 // rpcm localization_iterative for one point; returns lon/lat in degrees
 __device__ void localize(const RpcModel& r, double col, double row, double alt, double& lon_deg, double& lat_deg) {

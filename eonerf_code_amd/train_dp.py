@@ -13,12 +13,33 @@ StepLR gamma 0.9 per epoch, MSE for epoch < 2 then the uncertainty loss with the
 optional "water": [H,W] uint8, optional "sun": [elevation_deg, azimuth_deg] of the nadir camera's sun direction}.  With it, after
 every epoch (val_freq, train_eonerf.py:194) every rank checks its device status and rank 0 renders the nadir DSM, registers it on
 the ground truth and prints val/mae -- all on the GPU (eonerf_code_amd.dsm.evaluate_dsm).  Without it nothing changes.
+
+`--init_dsm` is a torch file {"dsm": [H,W] fp32 initial DSM, "bounds": [left, bottom, right, top] (UTM metres), "zone", "south",
+"scene_offset": [3], "scene_scale": [3], "rpcs": one rpcm dict per image at the table's downscale, "shapes": [n_img, 2], optional
+"conf": [H,W]} -- the reference's --init_dsm_path / --init_conf_path (opt.py:88-91) as tensors.  With it every rank builds the depth
+priors of the whole table on its own device at start-up (eonerf_code_amd.priors.depth_priors_from_dsm; deterministic, hence the same
+on every rank), carries them as a RayTable extra and adds metrics.depth_loss_L2 with weight --w_depth, multiplied by 0.8 after every
+epoch (train_eonerf.py:94,145-149,305-306); the status line gains train/depth_l2 and depth_weight.  Each rank takes the masked mean
+over its own rays.  Without it nothing changes.
 """
 import argparse
 import os
 import time
 
 import torch
+
+
+def depth_prior_term(extras, w_depth, record=None):
+    """The aux_loss of one batch (train_eonerf.py:145-149): metrics.depth_loss_L2 of the batch's priors (RayTable extras "prior_depth",
+    optional "prior_conf") on the rendered depth, column 3 of the packed outputs.  record: a one-element list that receives the term."""
+    from .priors import depth_loss_L2
+
+    def aux(out):
+        term = depth_loss_L2(extras["prior_depth"], out[:, 3], extras.get("prior_conf"), w_depth)
+        if record is not None:
+            record[0] = term.detach()
+        return term
+    return aux
 
 
 def main():
@@ -37,6 +58,8 @@ def main():
     ap.add_argument("--dump_params", default=None, help="write the final flat parameters of every rank to <path>.rank<r>")
     ap.add_argument("--gt_dsm", default=None, help="torch file with the lidar DSM, its ROI and the scene normalisation: DSM MAE after every epoch")
     ap.add_argument("--val_chunk", type=int, default=5120, help="rays per chunk of the validation render")
+    ap.add_argument("--init_dsm", default=None, help="torch file with an initial DSM, its bounds / UTM zone, the scene normalisation and the images' RPCs: depth supervision")
+    ap.add_argument("--w_depth", type=float, default=100.0, help="weight of the depth term (x 0.8 after every epoch)")
     args = ap.parse_args()
 
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -67,7 +90,20 @@ def main():
         rays, ts, rgbs = d["rays"], d["ts"], d["rgbs"]
     else:
         rays, ts, rgbs = synthetic_batch(args.synthetic_rays, args.n_images)
-    table = RayTable(rays, ts, rgbs, dev, seed=42, rank=rank, world=world)
+    extras = None
+    if args.init_dsm:
+        from .priors import depth_priors_from_dsm
+        p = torch.load(args.init_dsm, map_location="cpu")
+        for key in ("dsm", "bounds", "zone", "south", "scene_offset", "scene_scale", "rpcs", "shapes"):
+            if key not in p:
+                raise SystemExit(f"--init_dsm {args.init_dsm}: missing entry '{key}'")
+        conf = p["conf"].to(dev) if p.get("conf") is not None else None
+        prior, prior_conf = depth_priors_from_dsm(p["dsm"].to(dev), [float(x) for x in p["bounds"]], p["rpcs"], p["shapes"],
+                                                  rays.to(dev, torch.float32).contiguous(), p["scene_offset"], p["scene_scale"],
+                                                  int(p["zone"]), bool(p["south"]), conf=conf)
+        extras = {"prior_depth": prior} if prior_conf is None else {"prior_depth": prior, "prior_conf": prior_conf}
+    w_depth, depth_term = args.w_depth, [None]
+    table = RayTable(rays, ts, rgbs, dev, seed=42, rank=rank, world=world, extras=extras)
     field = EONerfMLP(args.n_images, radiometric_normalization=True, precision=args.precision).to(dev)
     trainer = FusedTrainer(field, lr=args.lr, max_rays=args.batch_size, keep_message=False, n_samples=args.n_samples)
     trainer.set_noise_seed(42 + 1000003 * rank)                              # per-rank jitter stream
@@ -84,20 +120,26 @@ def main():
     step, tic = 0, time.time()
     for epoch in range(10 ** 7):
         for i in range(steps_per_epoch):
-            r, im, px = table.batch(epoch, i, args.batch_size)
+            aux = None
+            if extras is None:
+                r, im, px = table.batch(epoch, i, args.batch_size)
+            else:
+                r, im, px, ex = table.batch(epoch, i, args.batch_size, with_extras=True)
+                aux = depth_prior_term(ex, w_depth, depth_term)
             nxt = None
             if trainer._exchanges() and i + 1 < steps_per_epoch:                     # the next batch's sampler runs under this step's gradient exchange
                 r2, im2, _ = table.batch(epoch, i + 1, args.batch_size)
-                nxt = (r2, im2, epoch)
-            loss = trainer.step(r, im, px, epoch, next_batch=nxt)
+                nxt = (r2, im2, epoch) if extras is None else (r2, im2, epoch, True)
+            loss = trainer.step(r, im, px, epoch, next_batch=nxt, aux_loss=aux)
             if step % args.check_every == 0:                                # the only host sync, every 1000 steps (:173-178)
                 # on EVERY rank: raises (-> non-zero exit of the job) if a device-side hand-off timed out on ANY rank since the last
                 # check; the fault flag of the gradient message has kept all replicas from applying an update since
                 trainer.check_device_status()
             if step % args.check_every == 0 and rank == 0:
                 el = time.time() - tic
+                prior_fields = "" if extras is None else f" | train/depth_l2={float(depth_term[0]):.5f} | depth_weight={w_depth:.6g}"
                 print(f"epoch={epoch} | elapsed_time={el:.2f}s | step={step} | loss={float(loss):.5f} | "
-                      f"rays/s={(step + 1) * args.batch_size * world / max(el, 1e-9):.0f}", flush=True)
+                      f"rays/s={(step + 1) * args.batch_size * world / max(el, 1e-9):.0f}{prior_fields}", flush=True)
             save_now = step > 0 and step % (4 * steps_per_epoch) == 0         # save_freq, :180-191 (the same decision on every rank)
             if save_now and step % args.check_every != 0:
                 # a checkpoint must not hold updates that were skipped: after a device-side fault the Adam kernel leaves the weights alone
@@ -123,6 +165,7 @@ def main():
                 mae, n_valid = mae.tolist()                                 # the validation's one read-back
                 print(f"epoch={epoch} | elapsed_time={time.time() - tic:.2f}s | step={step} | val/mae={mae:.4f} | val/cells={int(n_valid)}", flush=True)
         trainer.set_lr(trainer.lr * 0.9)                                    # StepLR(step_size=1, gamma=0.9), :64,304
+        w_depth *= 0.8                                                      # :305-306
 
 
 if __name__ == "__main__":

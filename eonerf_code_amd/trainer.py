@@ -353,17 +353,24 @@ class RayTable:
     Every rank holds the full table and walks its own slice of ONE shared per-epoch permutation (same seed everywhere) --
     what DataLoader(shuffle=True) does on a single GPU, sharded like a DistributedSampler."""
 
-    def __init__(self, rays, img_idx, rgbs, device, seed=42, rank=0, world=1):
+    def __init__(self, rays, img_idx, rgbs, device, seed=42, rank=0, world=1, extras=None):
+        """extras: optional {name: per-ray tensor [N, ...]} (depth priors, confidences) that travel with the rays: shuffled by the same
+        permutation in the same gather pass and returned by batch(..., with_extras=True)."""
         self.rays = rays.to(device, torch.float32).contiguous()
         self.img = img_idx.reshape(-1).to(device, torch.int64).contiguous()
         self.rgbs = rgbs.to(device, torch.float32).contiguous()
         self.n, self.seed, self.rank, self.world = self.rays.shape[0], seed, rank, world
         self._perm_epoch, self._perm, self._shuffled = None, None, None
+        self.extras = {k: v.to(device).contiguous() for k, v in (extras or {}).items()}
+        for k, v in self.extras.items():
+            if v.dim() < 1 or v.shape[0] != self.n:
+                raise ValueError(f"extras['{k}'] must have one row per ray")
+        self._shuffled_extras = {}
 
     def steps_per_epoch(self, batch_per_rank):
         return self.n // (batch_per_rank * self.world)
 
-    def batch(self, epoch, step, batch_per_rank):
+    def batch(self, epoch, step, batch_per_rank, with_extras=False):
         """Batch `step` of epoch `epoch` for this rank.  The shuffle is ONE on-device gather of the whole table per epoch (three
         index_select launches over the table, microseconds at 16 MB); a step's batch is then a contiguous slice of the shuffled
         copy -- no per-step gather kernels, no host work beyond slicing.  The shuffled copy doubles the table's footprint
@@ -374,7 +381,11 @@ class RayTable:
             g = torch.Generator(device=self.rays.device).manual_seed(self.seed + epoch)
             self._perm = torch.randperm(self.n, generator=g, device=self.rays.device)
             self._shuffled = (self.rays.index_select(0, self._perm), self.img.index_select(0, self._perm), self.rgbs.index_select(0, self._perm))
+            self._shuffled_extras = {k: v.index_select(0, self._perm) for k, v in self.extras.items()}
             self._perm_epoch = epoch
         lo = (step * self.world + self.rank) * batch_per_rank
         r, i, c = self._shuffled
+        if with_extras:     # a fourth element: {name: the same rows of every extra}
+            return (r[lo:lo + batch_per_rank], i[lo:lo + batch_per_rank], c[lo:lo + batch_per_rank],
+                    {k: v[lo:lo + batch_per_rank] for k, v in self._shuffled_extras.items()})
         return r[lo:lo + batch_per_rank], i[lo:lo + batch_per_rank], c[lo:lo + batch_per_rank]
