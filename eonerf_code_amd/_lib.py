@@ -31,6 +31,8 @@ DSM_SYMBOLS = ["eonerf_dsm_version", "eonerf_nadir_rays", "eonerf_dsm_rasterize"
                "eonerf_dsm_register", "eonerf_dsm_mae_workspace_bytes", "eonerf_dsm_mae"]
 # include/eonerf_prior.h: the stateless depth-prior group (initial DSM -> per-ray depth / confidence)
 PRIOR_SYMBOLS = ["eonerf_prior_version", "eonerf_prior_workspace_bytes", "eonerf_prior_reproject"]
+# include/eonerf_metrics.h: the stateless per-image validation metrics (uncertainty loss, MSE, PSNR)
+METRICS_SYMBOLS = ["eonerf_metrics_version", "eonerf_metrics_workspace_bytes", "eonerf_image_metrics"]
 
 
 class EonerfRpc(C.Structure):
@@ -53,6 +55,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_hip.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_dsm.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_prior.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_metrics.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -162,7 +165,11 @@ def lib():
     L.eonerf_prior_workspace_bytes.restype = sz
     L.eonerf_prior_workspace_bytes.argtypes = [i, i]
     L.eonerf_prior_reproject.argtypes = [vp, vp, i, i, d3, C.POINTER(EonerfRpc), i, i, i, i, vp, i, vp, i, fp, fp, vp, vp, sz, vp]
-    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS:
+    L.eonerf_metrics_version.restype = i
+    L.eonerf_metrics_workspace_bytes.restype = sz
+    L.eonerf_metrics_workspace_bytes.argtypes = []
+    L.eonerf_image_metrics.argtypes = [vp, i, vp, i, vp, i, C.c_long, vp, vp, sz, vp]
+    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS:
         getattr(L, name)
     _lib = L
     return L

@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--dump_params", default=None, help="write the final flat parameters of every rank to <path>.rank<r>")
     ap.add_argument("--gt_dsm", default=None, help="torch file with the lidar DSM, its ROI and the scene normalisation: DSM MAE after every epoch")
     ap.add_argument("--val_chunk", type=int, default=5120, help="rays per chunk of the validation render")
+    ap.add_argument("--val_images", default=None, help="torch file with held-out images (rays, rgbs, h, w): image loss and PSNR after every epoch")
+    ap.add_argument("--val_max", type=int, default=5, help="validation images rendered per epoch (train_eonerf.py:200)")
     ap.add_argument("--init_dsm", default=None, help="torch file with an initial DSM, its bounds / UTM zone, the scene normalisation and the images' RPCs: depth supervision")
     ap.add_argument("--w_depth", type=float, default=100.0, help="weight of the depth term (x 0.8 after every epoch)")
     args = ap.parse_args()
@@ -117,6 +119,18 @@ def main():
         if rank == 0:
             gt["dsm"] = gt["dsm"].to(dev, torch.float32)
             gt["water"] = gt["water"].to(dev, torch.uint8) if gt.get("water") is not None else None
+    val_images = None
+    if args.val_images:
+        v = torch.load(args.val_images, map_location="cpu")
+        if "images" not in v:
+            raise SystemExit(f"--val_images {args.val_images}: missing entry 'images'")
+        for k, im in enumerate(v["images"]):
+            for key in ("rays", "rgbs", "h", "w"):
+                if key not in im:
+                    raise SystemExit(f"--val_images {args.val_images}: image {k}: missing entry '{key}'")
+        if rank == 0:
+            val_images = [{"rays": im["rays"].to(dev, torch.float32), "rgbs": im["rgbs"].to(dev, torch.float32), "h": int(im["h"]),
+                           "w": int(im["w"])} for im in v["images"][:max(0, args.val_max)]]
     step, tic = 0, time.time()
     for epoch in range(10 ** 7):
         for i in range(steps_per_epoch):
@@ -164,6 +178,17 @@ def main():
                                    chunk=args.val_chunk, water=gt["water"])
                 mae, n_valid = mae.tolist()                                 # the validation's one read-back
                 print(f"epoch={epoch} | elapsed_time={time.time() - tic:.2f}s | step={step} | val/mae={mae:.4f} | val/cells={int(n_valid)}", flush=True)
+        if args.val_images:                                                 # the held-out images of the same block (:199-294)
+            if gt is None:
+                trainer.check_device_status()                               # on every rank (with --gt_dsm the check above has just run)
+            if rank == 0 and val_images:
+                from .validation import validate_images
+                _, means = validate_images(field, val_images, epoch, chunk=args.val_chunk, gt=gt, max_images=args.val_max)
+                names = ("loss", "coarse_color", "coarse_logbeta", "psnr") + (("mae",) if gt is not None else ())
+                vals = torch.stack([means[k] for k in names]).tolist()      # the validation's one read-back
+                line = (f"epoch={epoch} | elapsed_time={time.time() - tic:.2f}s | step={step} | val/loss={vals[0]:.5f} | "
+                        f"val/coarse_color={vals[1]:.5f} | val/coarse_logbeta={vals[2]:.5f} | val/psnr={vals[3]:.4f}")
+                print(line + (f" | val/img_mae={vals[4]:.4f}" if gt is not None else ""), flush=True)
         trainer.set_lr(trainer.lr * 0.9)                                    # StepLR(step_size=1, gamma=0.9), :64,304
         w_depth *= 0.8                                                      # :305-306
 

@@ -1,0 +1,117 @@
+"""Per-epoch validation on the device (include/eonerf_metrics.h): the block of train_eonerf.py:194-294 without leaving the GPU.
+
+Held-out images are rendered whole in the field's export precision (sat_rendering.render_image), metrics.uncertainty_aware_loss and
+metrics.psnr (metrics.py:17-22,60-69) are reduced per image by one library call, and -- where a lidar DSM exists -- a DSM is
+rasterised from each image's own rays and rendered depth, registered on the ground truth and its MAE taken (eonerf_code_amd.dsm).
+PyTorch owns the memory and the stream; every arithmetic step runs in libeonerf_hip.so.  Nothing here reads a result back.
+"""
+import math
+
+import torch
+
+from . import _lib
+from .radiance_fields.eonerf import _ptr, _stream
+
+COLUMNS = ("loss", "coarse_color", "coarse_logbeta", "mse", "psnr", "mae", "n")
+
+
+def _rows(t, cols):
+    """t as fp32 rows of `cols` contiguous floats -> (tensor to keep alive, n, stride in floats).  A column view of a packed [R, 21]
+    render output (and any other fp32 rows with unit column stride) passes through without a copy."""
+    if t.dim() < 1 or t.shape[-1] != cols or not t.is_cuda:
+        raise ValueError(f"expected a GPU tensor of shape [..., {cols}], got {tuple(t.shape)} on {t.device}")
+    if not (t.dim() == 2 and t.dtype == torch.float32 and t.shape[0] > 0 and (cols == 1 or t.stride(1) == 1)
+            and (t.shape[0] == 1 or t.stride(0) >= cols)):
+        t = t.reshape(-1, cols).to(torch.float32).contiguous()
+    return t, t.shape[0], (t.stride(0) if t.shape[0] > 1 else cols)
+
+
+def image_metrics(pred_rgb, gt_rgb, beta=None):
+    """metrics.uncertainty_aware_loss(gt_rgb, pred_rgb, beta) and metrics.mse / psnr(pred_rgb, gt_rgb) of one image ->
+    device double[6] = loss, coarse_color, coarse_logbeta, mse, psnr, n (eonerf_image_metrics; fp64 sums in a fixed order, run-to-run
+    bit-identical).  pred_rgb, gt_rgb [..., 3], beta [..., 1] or None (the first three entries are NaN then).  results["rgb"] /
+    results["beta"] of render_image are read in place from the packed render output."""
+    rgb, n, rgb_stride = _rows(pred_rgb, 3)
+    gt, n_gt, gt_stride = _rows(gt_rgb.to(rgb.device), 3)
+    if n_gt != n:
+        raise ValueError("one ground-truth colour per predicted colour")
+    b, beta_stride = None, 0
+    if beta is not None:
+        b, n_b, beta_stride = _rows(beta, 1)
+        if n_b != n:
+            raise ValueError("one beta per predicted colour")
+    L = _lib.lib()
+    out = torch.empty(6, dtype=torch.float64, device=rgb.device)
+    ws = torch.empty(L.eonerf_metrics_workspace_bytes(), dtype=torch.uint8, device=rgb.device)
+    with torch.cuda.device(rgb.device):
+        _lib.check(L.eonerf_image_metrics(_ptr(rgb), int(rgb_stride), _ptr(b), int(beta_stride), _ptr(gt), int(gt_stride), n, _ptr(out),
+                                          _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def _step_size_of(field):
+    """The render_step_size whose int(2 / step) is the field's current sample count."""
+    step = 2.0 / field._n_samples
+    return math.nextafter(step, 0.0) if int(2 / step) < field._n_samples else step
+
+
+def validate_images(field, images, epoch_idx, chunk=5120, render_step_size=None, gt=None, max_images=5, noise=None):
+    """The validation loop of train_eonerf.py:197-294 over images = [{"rays": [h*w, 11], "rgbs": [h*w, 3], "h", "w"}, ...], the first
+    min(max_images, len(images)) of them (:200).  Per image: render_image under no_grad with the module in .eval() mode -- i.e. in
+    the field's export precision -- with epoch_idx and chunk as given, then image_metrics on results["rgb"] / results["beta"].
+
+    gt: None, or the dict train_dp.py --gt_dsm loads ("dsm", "roi", "scene_offset", "scene_scale", optional "water").  With it the
+    image's DSM MAE (:259-289): rasterize_dsm of the image's own rays and rendered depth on the ROI's grid, water mask,
+    register_dsm(scaling=False), dsm_mae.
+
+    Returns (table, means): table is a device double [n_images, 7] of loss, coarse_color, coarse_logbeta, mse, psnr, mae (NaN
+    without gt), n; means maps the first six names to device scalars.  The only host synchronisation is render_image's own sample
+    count; the caller reads the means once.  The caller's train / eval mode is restored.
+
+    Two quirks of the reference are kept.  (1) Every validation image is rendered with image index 0 (ts = zeros_like, :207): the
+    transient embedding and the radiometric correction are those of training image 0, whatever image is shown.  (2) Image 0 is the
+    reference's "train" image (:246-249) and is left out of the means (`if i != 0`, :259) -- when there is more than one image; a
+    single image is its own mean.
+    One deliberate deviation: the reference appends to its means only when a ground-truth DSM exists (`and args.gt_dir is not None`,
+    :259), so without one it logs no val/loss or val/psnr at all; here the image metrics are reported without a ground truth too.
+
+    noise: None (production: the sampler kernels draw the jitter) or one render_image `noise` argument per image (parity tests)."""
+    from .datasets.satellite import define_satrays_from_tensors
+    from .sat_rendering import render_image
+    images = list(images)[:max(0, int(max_images))]
+    if not images:
+        raise ValueError("validate_images: no images")
+    if render_step_size is None:
+        render_step_size = _step_size_of(field)
+    dev = next(field.parameters()).device
+    if gt is not None:
+        from .dsm import dsm_mae, mask_water, rasterize_dsm, register_dsm
+        gt_dsm = gt["dsm"].to(dev, torch.float32)
+        water = gt["water"].to(dev, torch.uint8) if gt.get("water") is not None else None
+        roi = [float(x) for x in gt["roi"]]
+    table = torch.full((len(images), len(COLUMNS)), float("nan"), dtype=torch.float64, device=dev)
+    was_training = field.training
+    field.eval()                                                            # :197
+    try:
+        with torch.no_grad():
+            for i, data in enumerate(images):
+                rays = data["rays"].to(dev, torch.float32).contiguous()
+                pixels = data["rgbs"].to(dev, torch.float32).reshape(-1, 3)
+                if rays.dim() != 2 or rays.shape[1] != 11 or rays.shape[0] != int(data["h"]) * int(data["w"]) or pixels.shape[0] != rays.shape[0]:
+                    raise ValueError(f"validate_images: image {i} needs rays [h*w, 11] and rgbs [h*w, 3]")
+                ts = torch.zeros(rays.shape[0], 1, dtype=torch.int64, device=dev)           # :207 -- image index 0 for every image
+                results, _ = render_image(field, None, define_satrays_from_tensors(rays, ts), None, None, epoch_idx=epoch_idx, chunk=chunk,
+                                          render_step_size=render_step_size, noise=None if noise is None else noise[i])
+                m = image_metrics(results["rgb"], pixels, results["beta"])                  # :229-230
+                table[i, 0:5] = m[0:5]
+                table[i, 6] = m[5]
+                if gt is not None:                                                          # :259-289
+                    dsm = rasterize_dsm(rays, results["depth"].reshape(-1), gt["scene_offset"], gt["scene_scale"], roi=roi)
+                    if water is not None:
+                        dsm = mask_water(dsm, water)
+                    table[i, 5] = dsm_mae(gt_dsm, dsm, register_dsm(gt_dsm, dsm, scaling=False))[0]
+    finally:
+        field.train(was_training)
+    rows = table[1:] if table.shape[0] > 1 else table                                       # :259, `if i != 0`
+    mean = rows.mean(dim=0)                                                                 # :293
+    return table, {name: mean[k] for k, name in enumerate(COLUMNS[:6])}

@@ -1,0 +1,75 @@
+"""CPU: the numpy restatement of the validation metrics (tests/metrics_restated.py) against golden G6, the reference's own
+uncertainty_aware_loss / psnr / mse outputs -- and the binding's symbol list against the new header.
+
+Bounds.  The G6 values are fp32 sums of 120 terms: worst case 120 x 2^-24 = 7e-6 relative, times 3 for the per-term roundings
+-> 2e-5 relative.  psnr = -10 log10(mse), so its absolute bound is 10 / ln 10 times the relative mse bound: 1e-4 dB."""
+import os
+import re
+
+import numpy as np
+
+from conftest import REPO, load_golden
+import metrics_restated as M
+
+REL, PSNR_ABS = 2e-5, 1e-4
+assert 10 / np.log(10) * REL <= PSNR_ABS
+
+
+def rel(got, want):
+    return abs(float(got) - float(want)) / abs(float(want))
+
+
+def test_restatement_matches_golden_g6():
+    g = load_golden("g6_metrics")
+    out = M.image_metrics(g["pred"], g["gt"], g["beta"])
+    for k, name in ((0, "unc_loss"), (1, "unc_color"), (2, "unc_logbeta"), (3, "mse")):
+        print(f"{name}: restated {out[k]:.9f}, reference {float(g[name]):.9f}, relative {rel(out[k], g[name]):.2e}")
+        assert rel(out[k], g[name]) <= REL, name
+    print(f"psnr: restated {out[4]:.7f}, reference {float(g['psnr']):.7f}")
+    assert abs(out[4] - float(g["psnr"])) <= PSNR_ABS
+    assert out[5] == g["pred"].shape[0] == 40
+
+
+def test_mse_equals_the_reference_torch_mse():
+    g = load_golden("g6_metrics")
+    out = M.image_metrics(g["pred"], g["gt"], g["beta"])
+    assert rel(out[3], g["mse_torch"]) <= REL
+
+
+def test_without_beta_the_loss_terms_are_nan():
+    g = load_golden("g6_metrics")
+    out = M.image_metrics(g["pred"], g["gt"])
+    assert np.isnan(out[:3]).all()
+    with_beta = M.image_metrics(g["pred"], g["gt"], g["beta"])
+    assert out[3] == with_beta[3] and out[4] == with_beta[4] and out[5] == 40
+
+
+def test_identical_images_have_infinite_psnr():
+    g = load_golden("g6_metrics")
+    out = M.image_metrics(g["gt"], g["gt"], g["beta"])
+    assert out[3] == 0.0 and out[4] == np.inf and out[1] == 0.0
+    assert rel(out[2], g["unc_logbeta"]) <= REL and out[0] == out[2]
+
+
+def test_restatement_imports_nothing_from_the_product_path():
+    src = open(os.path.join(REPO, "tests", "metrics_restated.py")).read()
+    assert re.findall(r"^\s*(?:import|from)\s+(\S+)", src, flags=re.M) == ["numpy"]
+
+
+def test_metrics_header_symbols_are_bound_and_exported():
+    import ctypes
+    from eonerf_code_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    hdr = open(os.path.join(REPO, "include", "eonerf_metrics.h")).read()
+    declared = set(re.findall(r"\b(eonerf_[a-z_]+)\s*\(", hdr))
+    assert declared == set(_lib.METRICS_SYMBOLS) and len(declared) == 3
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    for name in declared:
+        assert hasattr(L, name), name
+    L.eonerf_metrics_version.restype = ctypes.c_int
+    L.eonerf_metrics_workspace_bytes.restype = ctypes.c_size_t
+    assert L.eonerf_metrics_version() == 1
+    assert L.eonerf_metrics_workspace_bytes() == 256 * 4 * 8
+    L.eonerf_version.restype = ctypes.c_int
+    assert L.eonerf_version() == 502
