@@ -76,14 +76,17 @@ def generate_rays(rpc, min_alt, max_alt, h=None, w=None, cols=None, rows=None, i
     datasets/satellite.py:456-478); want_raw additionally (or alone) returns the un-normalised [N,8] rays of get_rays
     (:65-121), the payload of the reference's cache files.  Pixels: the full h x w grid, or explicit cols/rows.
     want_geo: returns ONLY the fp64 intermediates [N,8] (lon, lat, east, north at max_alt, then at min_alt) -- the values of
-    rpc.localization / utm_from_latlon before the fp32 cast of :119-120 (tests)."""
+    rpc.localization / utm_from_latlon before the fp32 cast of :119-120 (tests).
+    zone / south: the "+proj=utm +zone=<zone> [+south]" to project into.  Without `zone` they are chosen as the reference chooses
+    them (sat_utils.py:107-111, called at datasets/satellite.py:90,94): from the FIRST point of the call -- pixel (0, 0) of a grid,
+    element 0 of a list -- localised at max_alt, which costs one extra one-pixel launch and a read-back (set-up time only).  The
+    reference chooses again for the min_alt points; where that choice differs, its rays would join two projections, and a
+    ValueError is raised here instead."""
     import ctypes as C
     import torch
     from .. import _lib
     from ..radiance_fields.eonerf import _ptr, _stream
     s = _rpc_struct(rpc, img_downscale)
-    if zone is None:
-        zone, south = utm_zone_from_lonlat(s.lon_offset, s.lat_offset)
     dev = torch.device(device)
     if cols is not None:
         c = torch.as_tensor(cols, dtype=torch.float64).reshape(-1).to(dev).contiguous()
@@ -93,15 +96,30 @@ def generate_rays(rpc, min_alt, max_alt, h=None, w=None, cols=None, rows=None, i
         c = r = None
         n, width = int(h) * int(w), int(w)
     normalise = scene_offset is not None
-    rays = torch.empty(n, 11, dtype=torch.float32, device=dev) if normalise else None
-    raw = torch.empty(n, 8, dtype=torch.float32, device=dev) if (want_raw or not normalise) else None
     off = (C.c_float * 3)(*[float(x) for x in scene_offset]) if normalise else None
     sc = (C.c_float * 3)(*[float(x) for x in scene_scale]) if normalise else None
+
+    def launch(c, r, n, zone, south, raw, rays, geo):
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().eonerf_generate_rays(C.byref(s), _ptr(c), _ptr(r), n, width, float(min_alt), float(max_alt), int(zone),
+                                                       1 if south else 0, float(sun_elevation_deg or 0.0), float(sun_azimuth_deg or 0.0),
+                                                       off, sc, _ptr(raw), _ptr(rays), _ptr(geo), _stream()))
+
+    if zone is None and n == 0:
+        zone, south = utm_zone_from_lonlat(s.lon_offset, s.lat_offset)      # no point to ask; nothing is written either
+    elif zone is None:
+        first = torch.empty(1, 8, dtype=torch.float64, device=dev)
+        launch(None if c is None else c[:1], None if r is None else r[:1], 1, 1, False, None, None, first)      # any zone: lon / lat only
+        lon_hi, lat_hi, _, _, lon_lo, lat_lo, _, _ = first[0].tolist()
+        zone, south = utm_zone_from_lonlat(lon_hi, lat_hi)
+        if utm_zone_from_lonlat(lon_lo, lat_lo) != (zone, south):
+            z_lo, s_lo = utm_zone_from_lonlat(lon_lo, lat_lo)
+            raise ValueError(f"the first pixel lies in UTM zone {zone}{'S' if south else 'N'} at max_alt (lon {lon_hi}, lat {lat_hi}) but in "
+                             f"zone {z_lo}{'S' if s_lo else 'N'} at min_alt (lon {lon_lo}, lat {lat_lo}): pass zone= / south= explicitly")
+    rays = torch.empty(n, 11, dtype=torch.float32, device=dev) if normalise else None
+    raw = torch.empty(n, 8, dtype=torch.float32, device=dev) if (want_raw or not normalise) else None
     geo = torch.empty(n, 8, dtype=torch.float64, device=dev) if want_geo else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().eonerf_generate_rays(C.byref(s), _ptr(c), _ptr(r), n, width, float(min_alt), float(max_alt), int(zone),
-                                                   1 if south else 0, float(sun_elevation_deg or 0.0), float(sun_azimuth_deg or 0.0),
-                                                   off, sc, _ptr(raw), _ptr(rays), _ptr(geo), _stream()))
+    launch(c, r, n, zone, south, raw, rays, geo)
     if want_geo:
         return geo
     if normalise and want_raw:

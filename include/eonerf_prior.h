@@ -54,7 +54,8 @@ size_t eonerf_prior_workspace_bytes(int out_h, int out_w);
  *   One call with `values` = the confidence therefore yields the depth prior AND the reprojected confidence of an image; the
  *   reference runs the reprojection twice and gets the same winners.
  *
- * PARITY UNPINNED for the inverse UTM: pyproj / PROJ are not vendored with the reference.  It is restated from the published
+ * Inverse UTM: pyproj / PROJ are not vendored with the reference; pinned by a definition-based arbitrary-precision transverse Mercator
+ * (tests/geodesy_exact.py, tests/test_geodesy_gpu.py; pyproj itself still absent).  It is restated from the published
  * algorithm PROJ's etmerc implements (Karney 2011: the 6th-order Krueger series with the beta coefficients, then Newton on
  * tau = tan(lat) from the conformal latitude, a fixed five iterations); the forward series of eonerf_generate_rays has the same
  * status.  tests/prior_restated.py is the contract; the rest is pinned by golden g13, recorded from the reference's own code.

@@ -3,14 +3,16 @@
 Follows datasets/satellite.py:57-139,456-458,486-500 (get_rays, normalize_rays, get_dir_vec_from_el_az,
 get_sun_dirs) and sat_utils.py:41-59,99-116,437-450 (rescale_rpc, utm_from_latlon, apply_poly) of the reference.
 
-PARITY STATUS: **unpinned**.  The two numerical cores live in un-vendored third-party packages that are absent from
-/root/reference and from this image, and the reference ships no fixture for them:
+PARITY STATUS: rpcm **unpinned**; the UTM leg **pinned by a definition-based arbitrary-precision transverse Mercator**
+(tests/geodesy_exact.py, tests/test_geodesy_exact_cpu.py; pyproj itself still absent).  The two numerical cores live in un-vendored
+third-party packages that are absent from the reference tree and from this image, and the reference ships no fixture for them:
   * rpcm (requirements.txt:8, unpinned) RPCModel.localization -> restated below from its published iterative
     algorithm (localization_iterative: a base of two EPS steps in normalised lon/lat is projected into the image and the
     residual is decomposed on it; EPS = 2 for the first iteration, 0.1 afterwards; stop when the squared normalised
     image residual is < 1e-18).  The polynomial term order is pinned by the in-tree copy sat_utils.py:437-450.
   * pyproj 3.0.1 / PROJ (setup_env.sh:11) "+proj=utm": restated as the 6th-order Krueger series (Karney 2011), the
     algorithm PROJ's etmerc implements; agreement with PROJ is at the nanometre level by construction of the series.
+    utm_forward is within 1e-7 m (measured: 5.6e-9 m) of the projection's definition evaluated in 40-digit arithmetic.
 In-tree anchors used by tests/test_raygen.py: apply_poly term order, the normalisation / sun-direction formulas, the
 fp32 round trip at datasets/satellite.py:119-120, and the property projection(localization(x)) == x.
 """
@@ -57,8 +59,10 @@ def projection(rpc, lon, lat, alt):
     return col, row
 
 
-def localization(rpc, col, row, alt, max_iter=100):
-    """rpcm RPCModel.localization_iterative restated (see module docstring)."""
+def localization(rpc, col, row, alt, max_iter=100, per_point=False):
+    """rpcm RPCModel.localization_iterative restated (see module docstring).  Like rpcm it iterates EVERY point of the call until the
+    slowest has met the stopping rule.  per_point=True freezes each point once its own residual meets the rule -- what a kernel with
+    one thread per pixel does, and bit for bit what one call per point returns; the two ends differ by up to 1e-9 normalised."""
     col, row, alt = (np.asarray(v, dtype=np.float64) for v in (col, row, alt))
     ncol = (col - rpc["col_offset"]) / rpc["col_scale"]
     nrow = (row - rpc["row_offset"]) / rpc["row_scale"]
@@ -74,12 +78,13 @@ def localization(rpc, col, row, alt, max_iter=100):
     while not np.all((x0 - ncol) ** 2 + (y0 - nrow) ** 2 < 1e-18):
         if n > max_iter:
             raise RuntimeError("max localization iterations exceeded")
+        go = ((x0 - ncol) ** 2 + (y0 - nrow) ** 2 >= 1e-18) if per_point else True
         e1x, e1y, e2x, e2y = x1 - x0, y1 - y0, x2 - x0, y2 - y0
         ux, uy = ncol - x0, nrow - y0
         a1 = (ux * e1x + uy * e1y) / (e1x * e1x + e1y * e1y)
         a2 = (ux * e2x + uy * e2y) / (e2x * e2x + e2y * e2y)
-        lon = lon + a1 * eps
-        lat = lat + a2 * eps
+        lon = np.where(go, lon + a1 * eps, lon)
+        lat = np.where(go, lat + a2 * eps, lat)
         eps = 0.1
         x0, y0 = apply_rfm(cn, cd, lat, lon, nalt), apply_rfm(rn, rd, lat, lon, nalt)
         x1, y1 = apply_rfm(cn, cd, lat, lon + eps, nalt), apply_rfm(rn, rd, lat, lon + eps, nalt)
@@ -108,6 +113,25 @@ def utm_zone_number(lat, lon):
         if lon < 42:
             return 37
     return int((lon + 180) / 6) % 60 + 1
+
+
+def utm_zone_and_hemisphere(lat, lon):
+    """(zone number, south?) of one point as sat_utils.py:107-111 derives them: utm.latlon_to_zone_number and
+    utm.latitude_to_zone_letter(lat) < 'N' -- the letters C..M are the southern bands, so latitude 0 is north."""
+    return utm_zone_number(lat, lon), bool(lat < 0)
+
+
+def zone_of_first_point(rpc, col0, row0, min_alt, max_alt):
+    """The projection get_rays of the reference works in (datasets/satellite.py:89-94 -> sat_utils.py:107-111): utm_from_latlon takes
+    zone and hemisphere from element 0 of each call, once for the max_alt points and once for the min_alt points.  Where the two
+    differ the reference's rays would run between two projections: ValueError."""
+    lon, lat = localization(rpc, np.array([col0]), np.array([row0]), np.array([float(max_alt)]))
+    hi = utm_zone_and_hemisphere(float(lat[0]), float(lon[0]))
+    lon, lat = localization(rpc, np.array([col0]), np.array([row0]), np.array([float(min_alt)]))
+    lo = utm_zone_and_hemisphere(float(lat[0]), float(lon[0]))
+    if lo != hi:
+        raise ValueError(f"the first pixel lies in UTM zone {hi[0]}{'S' if hi[1] else 'N'} at max_alt but in {lo[0]}{'S' if lo[1] else 'N'} at min_alt")
+    return hi
 
 
 def krueger_alpha():
@@ -149,14 +173,15 @@ def get_dir_vec_from_el_az(elevation_deg, azimuth_deg):
     return -1.0 * np.array([np.sin(az) * np.cos(el), np.cos(az) * np.cos(el), np.sin(el)])
 
 
-def get_rays(cols, rows, rpc, min_alt, max_alt, zone, south=False):
-    """datasets/satellite.py:65-121 (utm branch): -> float32 [N,8] (o3, d3, near, far) incl. the fp32 cast at :119-120."""
+def get_rays(cols, rows, rpc, min_alt, max_alt, zone, south=False, per_point=False):
+    """datasets/satellite.py:65-121 (utm branch): -> float32 [N,8] (o3, d3, near, far) incl. the fp32 cast at :119-120.
+    per_point: see localization."""
     cols, rows = np.asarray(cols, dtype=np.float64), np.asarray(rows, dtype=np.float64)
     max_alts, min_alts = float(max_alt) * np.ones(cols.shape), float(min_alt) * np.ones(cols.shape)
-    lons, lats = localization(rpc, cols, rows, max_alts)
+    lons, lats = localization(rpc, cols, rows, max_alts, per_point=per_point)
     e, n = utm_forward(lats, lons, zone, south)
     near = np.vstack([e, n, max_alts]).T
-    lons, lats = localization(rpc, cols, rows, min_alts)
+    lons, lats = localization(rpc, cols, rows, min_alts, per_point=per_point)
     e, n = utm_forward(lats, lons, zone, south)
     far = np.vstack([e, n, min_alts]).T
     d = far - near

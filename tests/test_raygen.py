@@ -1,7 +1,8 @@
 """H1 / N2: RPC ray generation.  CPU part: the oracle's own consistency (projection o localisation = identity, the UTM series
 against closed-form anchors).  GPU part: the HIP kernel against the oracle.
 
-Parity status: UNPINNED w.r.t. rpcm / pyproj (un-vendored; oracle/raygen_oracle.py docstring).  Tolerance on the GPU path:
+Parity status: UNPINNED w.r.t. rpcm (un-vendored; oracle/raygen_oracle.py docstring); the UTM series is pinned by
+tests/geodesy_exact.py (tests/test_geodesy_exact_cpu.py, tests/test_geodesy_gpu.py).  Tolerance on the GPU path:
 the reference casts UTM coordinates to fp32 (datasets/satellite.py:119-120; northing ~3.3e6 m -> 0.25 m quantum) BEFORE
 normalising, so a 1e-9-relative difference between two fp64 evaluations can flip that rounding: values either agree to 1e-6
 (normalised units) or differ by exactly one fp32 quantum of the raw value; the test allows < 0.1 % such flips."""
@@ -186,7 +187,7 @@ def test_load_rays_cache_semantics_8_vs_11_columns_cpu(tmp_path):
         ds.load_rays(files, scene_loc=loc, cache_dir=str(cache), device="cpu")
 
 
-# ---- narrowing the unpinned surface of H1 / N2 (still parity-UNPINNED w.r.t. rpcm / pyproj: see the module docstring) -----------
+# ---- narrowing the unpinned surface of H1 / N2 (still parity-UNPINNED w.r.t. rpcm: see the module docstring) ---------------------
 def worldview_like_rpc(seed=0):
     """An RPC with the magnitudes of a WorldView-3 DFC2019 crop (datasets' JSON "rpc" entries): image normalisation of a few
     thousand pixels, ground footprint of ~0.02 deg, height scale 500 m, second-order terms ~1e-3, cubic terms ~1e-5, denominators
