@@ -33,6 +33,8 @@ DSM_SYMBOLS = ["eonerf_dsm_version", "eonerf_nadir_rays", "eonerf_dsm_rasterize"
 PRIOR_SYMBOLS = ["eonerf_prior_version", "eonerf_prior_workspace_bytes", "eonerf_prior_reproject"]
 # include/eonerf_metrics.h: the stateless per-image validation metrics (uncertainty loss, MSE, PSNR)
 METRICS_SYMBOLS = ["eonerf_metrics_version", "eonerf_metrics_workspace_bytes", "eonerf_image_metrics"]
+# include/eonerf_sweep.h: one view under K sun directions from one camera pass (relight.py)
+SWEEP_SYMBOLS = ["eonerf_sweep_version", "eonerf_sun_sweep_workspace_bytes", "eonerf_render_sun_sweep"]
 
 
 class EonerfRpc(C.Structure):
@@ -56,6 +58,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_dsm.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_prior.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_metrics.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_sweep.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -169,7 +172,11 @@ def lib():
     L.eonerf_metrics_workspace_bytes.restype = sz
     L.eonerf_metrics_workspace_bytes.argtypes = []
     L.eonerf_image_metrics.argtypes = [vp, i, vp, i, vp, i, C.c_long, vp, vp, sz, vp]
-    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS:
+    L.eonerf_sweep_version.restype = i
+    L.eonerf_sun_sweep_workspace_bytes.restype = sz
+    L.eonerf_sun_sweep_workspace_bytes.argtypes = [vp, i, i]
+    L.eonerf_render_sun_sweep.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
+    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS:
         getattr(L, name)
     _lib = L
     return L

@@ -3,6 +3,7 @@
 // under the address + undefined-behaviour sanitizers).  The caller (PyTorch) owns the workspace; these functions only lay it out.
 #pragma once
 #include <stdint.h>
+#include <limits.h>
 #include <string.h>
 #include <algorithm>
 #include "../../include/eonerf_hip.h"
@@ -139,6 +140,23 @@ inline RenderWs carve_render(const CarveCfg& cfg, void* base, int n_rays, int fl
     if (shadows && !od) carve_pass(c, w.sun, n_rays, p_cap, false, train, true, ab); else memset(&w.sun, 0, sizeof(w.sun));
     w.bytes = c.off + 256;
     return w;
+}
+
+// ---- eonerf_render_sun_sweep (include/eonerf_sweep.h): one camera pass, then a shadow pass per sun direction ----
+// The bound of a sweep on its batch, in 64 bits: p_cap_of must not wrap, i.e. n_rays x (n_samples - 1) rounded up to 256 stays an int
+inline bool sweep_rays_addressable(int n_rays, int n_samples) { return (long long)n_rays * (n_samples - 1) <= (long long)INT_MAX - 255; }
+
+struct SweepWs { RenderWs r; float* table; size_t bytes; };
+// carve_render(EONERF_F_SHADOWS) unchanged -- every launch of the forward sees the forward's layout -- followed by the sweep's own
+// copy of the ray table ([n_rays][11]: columns 8..10 hold the current sun).  The layout does not depend on the number of suns
+inline SweepWs carve_sweep(const CarveCfg& cfg, void* base, int n_rays) {
+    SweepWs s;
+    s.r = carve_render(cfg, base, n_rays, EONERF_F_SHADOWS);
+    Carver c(base);
+    c.off = s.r.bytes - 256;      // (where carve_render's own allocator stopped)
+    s.table = c.take<float>((size_t)n_rays * 11);
+    s.bytes = c.off + 256;
+    return s;
 }
 
 // Everything a pipelined backward call needs zeroed, as ONE span: [bottleneck factors | GEMM work queue | the PIPE_LAUNCHES sync blocks].

@@ -1,6 +1,7 @@
 // Sampling, rendering and the training step (eonerf_sample_rays, eonerf_rendering*, eonerf_presample*, eonerf_render_*): entry points of
 // libeonerf_hip.so (include/eonerf_hip.h).  Host logic only: argument blocks and kernel sequencing over the caller's workspace.
 #include "eonerf_ctx.h"
+#include "eonerf_render_args.h"
 
 int eo_run_mlp_fwd(eonerf_ctx* ctx, const PassBuffers& b, const float* flat, int p_cap, bool full, int mode, hipStream_t st, int prof_id, bool render_train) {
     if (!full) { const int rc = eo_ensure_density_streams(ctx, flat, st); if (rc) return rc; }
@@ -97,17 +98,6 @@ static EmbGradArgs emb_grad_args(const eonerf_ctx* ctx, const RenderWs& w, const
     eg.offsets = w.cam.offsets; eg.counts = w.cam.counts; eg.img_idx = img_idx; eg.g_emb = w.cam.g_emb; eg.d_emb = d_flat + ctx->pl.t[ctx->pl.emb].offset; eg.n_rays = n_rays;
     eg.lds_images = ctx->cfg.n_images <= 4096 ? ctx->cfg.n_images : 0; eg.d_emb_rays = d_emb_rays;
     return eg;
-}
-// camera pass compositing; w.amb_save is null outside training
-static CompositeArgs composite_args(const eonerf_ctx* ctx, const RenderWs& w, const float* flat, const float* rays, int n_rays, int p_cap, bool depth_only) {
-    CompositeArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.n_samples = ctx->n_samples;
-    ca.rays = rays; ca.offsets = w.cam.offsets; ca.counts = w.cam.counts;
-    ca.sigma = w.cam.sigma; ca.delta = w.cam.delta; ca.tmid = w.cam.tmid; ca.albedo = w.cam.albedo; ca.ts = w.cam.ts; ca.tb = w.cam.tb;
-    ca.p_pad = p_cap; ca.n_rays = n_rays; ca.depth_only = depth_only ? 1 : 0; ca.amb = ambient_w(ctx, flat); ca.ray_out = w.ray_rec;
-    ca.amb_save = depth_only ? nullptr : w.amb_save;
-    return ca;
 }
 static PackedArgs packed_args(const RenderWs& w, const float* rays, const int64_t* img_idx, const float* t_starts, const float* t_ends, const int64_t* ray_indices, int n, int n_rays) {
     PackedArgs pa;
@@ -291,22 +281,6 @@ int eonerf_rendering_backward(eonerf_ctx* ctx, const float* flat, const float* r
     return camera_backward(ctx, w, flat, rays, img_idx, n_rays, p_cap, d_flat, true, !depth_only, true, nullptr, depth_only != 0, st);
 }
 
-// Arguments of the camera pass's sampler launch (eonerf_render_forward, eonerf_presample); the Philox call number is the caller's
-static SampleArgs camera_sample_args(const eonerf_ctx* ctx, const RenderWs& w, const float* rays, const int64_t* img_idx, const float* zsteps,
-                                     const float* u_cam, const float* u_retry, int n_rays, int* n_samples_dev) {
-    SampleArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.n_samples = ctx->n_samples;
-    sa.rays = rays; sa.img_idx = img_idx; sa.zsteps = zsteps; sa.u = u_cam; sa.u_retry = u_retry;
-    sa.perturb = 1; sa.retry = (!u_cam || u_retry) ? 1 : 0;
-    if (!u_cam) sa.seed = ctx->noise_seed;
-    sa.n_rays = n_rays; sa.sun_pass = 0; sa.patch_last = 1;
-    sa.cnt_first = w.cnt_first; sa.cnt_retry = w.cnt_retry; sa.counts = w.cam.counts; sa.offsets = w.cam.offsets;
-    sa.flags = w.flags; sa.n_pts = w.cam.n_pts; sa.n_pts_copy = n_samples_dev;       // the scan kernel also fills the caller's count
-    sa.px = w.cam.px; sa.py = w.cam.py; sa.pz = w.cam.pz; sa.tmid = w.cam.tmid; sa.delta = w.cam.delta; sa.simg = w.cam.simg;
-    return sa;
-}
-
 /* The camera pass's sampler of the NEXT eonerf_render_forward(EONERF_F_TRAIN, production noise), launched ahead of it: it reads the rays and
  * the seed only, so a data-parallel trainer runs it on the compute stream while the gradient all-reduce of the step before is in flight
  * (the exchange's serial tail).  The workspace must be free (the backward that used it has been enqueued on `stream`). */
@@ -375,22 +349,10 @@ int eonerf_render_forward(eonerf_ctx* ctx, const float* flat, const float* rays,
     const bool rgb_loss = train && !shadows && (flags & EONERF_F_RGB_LOSS);
     int rc = eo_run_mlp_fwd(ctx, w.cam, flat, p_cap, !od, train ? (rgb_loss ? 2 : 1) : 0, st, EONERF_PROF_FWD_CHAIN_CAMERA, train);
     if (rc) return rc;
-    CompositeArgs ca = composite_args(ctx, w, flat, rays, n_rays, p_cap, od);
-    // irradiance model + radiometric affine + packing (sat_rendering.py:265-312): done by the chunk's LAST compositing launch, ray by ray
-    ShadeArgs sh;
-    sh.ray_rec = w.ray_rec; sh.img_idx = img_idx;
-    sh.radiometric = ctx->cfg.radiometric ? flat + ctx->pl.t[ctx->pl.rad].offset : nullptr;
-    sh.pts_first = w.cnt_first; sh.sc_counts = shadows ? w.sun.counts : w.cnt_first;
-    sh.n_rays = n_rays; sh.use_shadow = shadows ? 1 : 0; sh.eval = (flags & EONERF_F_EVAL) ? 1 : 0; sh.out = out;
-    ca.shade = sh; ca.do_shade = shadows ? 0 : 1;
-    // sun pass: shadow rays from the rendered surface toward the sun; the camera compositing counts their samples
-    SampleArgs ss = sa;
-    ss.img_idx = nullptr; ss.u = u_sun; ss.u_retry = nullptr; ss.retry = 0;
-    ss.depth = w.ray_rec + RR_DEPTH; ss.depth_stride = RAY_REC; ss.sun_pass = 1; ss.patch_last = 0;
-    ss.cnt_first = w.sun.counts; ss.cnt_retry = w.cnt_retry; ss.counts = w.sun.counts; ss.offsets = w.sun.offsets;
-    ss.n_pts = w.sun.n_pts; ss.n_pts_copy = nullptr;
-    ss.px = w.sun.px; ss.py = w.sun.py; ss.pz = w.sun.pz; ss.tmid = w.sun.tmid; ss.delta = w.sun.delta; ss.simg = w.sun.simg;
-    if (shadows) { ca.count_sun = 1; ca.sun = ss; }
+    // the chunk's LAST compositing launch shades; with the shadow pass on, the camera compositing counts the shadow rays' samples
+    const ShadeArgs sh = shade_args(ctx, w, flat, img_idx, n_rays, shadows, flags, out);
+    const SampleArgs ss = sun_sample_args(sa, w, u_sun);
+    const CompositeArgs ca = camera_composite_args(ctx, w, flat, rays, n_rays, p_cap, od, sh, shadows, ss);
     HIP_TRY(eo_launch_composite_fwd(ca, st));
 
     // ---- sun pass ---------------------------------------------------------------------------------------------
@@ -398,10 +360,7 @@ int eonerf_render_forward(eonerf_ctx* ctx, const float* flat, const float* rays,
         HIP_TRY(eo_launch_sampler(ss, st, true));
         rc = eo_run_mlp_fwd(ctx, w.sun, flat, p_cap, false, train ? 1 : 0, st, EONERF_PROF_FWD_CHAIN_SUN, train);
         if (rc) return rc;
-        CompositeArgs cs = ca;
-        cs.offsets = w.sun.offsets; cs.counts = w.sun.counts; cs.sigma = w.sun.sigma; cs.delta = w.sun.delta; cs.tmid = w.sun.tmid;
-        cs.shadow_only = 1; cs.depth_only = 0; cs.count_sun = 0; cs.do_shade = 1;
-        HIP_TRY(eo_launch_composite_fwd(cs, st));
+        HIP_TRY(eo_launch_composite_fwd(shadow_composite_args(ca, w), st));
     }
     return EONERF_OK;
 }
