@@ -35,6 +35,9 @@ PRIOR_SYMBOLS = ["eonerf_prior_version", "eonerf_prior_workspace_bytes", "eonerf
 METRICS_SYMBOLS = ["eonerf_metrics_version", "eonerf_metrics_workspace_bytes", "eonerf_image_metrics"]
 # include/eonerf_sweep.h: one view under K sun directions from one camera pass (relight.py)
 SWEEP_SYMBOLS = ["eonerf_sweep_version", "eonerf_sun_sweep_workspace_bytes", "eonerf_render_sun_sweep"]
+# include/eonerf_occ.h: the occupancy grid (occupancy.py) -- update, dilation, the grid of a context's export renders, the pinned sampler
+OCC_SYMBOLS = ["eonerf_occ_version", "eonerf_occ_workspace_bytes", "eonerf_occ_update", "eonerf_occ_dilate", "eonerf_set_occupancy",
+               "eonerf_occ_sample_rays"]
 
 
 class EonerfRpc(C.Structure):
@@ -59,6 +62,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_prior.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_metrics.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_sweep.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_occ.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -176,7 +180,14 @@ def lib():
     L.eonerf_sun_sweep_workspace_bytes.restype = sz
     L.eonerf_sun_sweep_workspace_bytes.argtypes = [vp, i, i]
     L.eonerf_render_sun_sweep.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
-    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS:
+    L.eonerf_occ_version.restype = i
+    L.eonerf_occ_workspace_bytes.restype = sz
+    L.eonerf_occ_workspace_bytes.argtypes = [vp, i]
+    L.eonerf_occ_update.argtypes = [vp, vp, vp, vp, i, fp, fp, fp, i, C.c_uint32, vp, vp, vp, sz, vp]
+    L.eonerf_occ_dilate.argtypes = [vp, vp, i, vp]
+    L.eonerf_set_occupancy.argtypes = [vp, vp, i]
+    L.eonerf_occ_sample_rays.argtypes = [vp, vp, vp, vp, i, i, vp, i, vp, vp, vp, vp, vp, vp, sz, vp]
+    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS:
         getattr(L, name)
     _lib = L
     return L

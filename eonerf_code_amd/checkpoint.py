@@ -3,9 +3,13 @@
     torch.save({'epoch', 'occ_grid_state_dict', 'model_state_dict', 'optimizer_state_dict', 'loss'}, 'ckpts/epoch=<e>.ckpt')
 
 `model_state_dict` has the reference's 44 keys, `optimizer_state_dict` is a torch.optim.Adam state_dict over
-named_parameters() order (so the reference could resume from it), and `occ_grid_state_dict` is the inert nerfacc
-OccGridEstimator state the reference's eval script insists on loading (the grid never influences a rendered value,
-SURVEY.md 0)."""
+named_parameters() order (so the reference could resume from it), and `occ_grid_state_dict` is the nerfacc OccGridEstimator
+state the reference's eval script insists on loading: four buffers, `resolution` int32 [3], `aabbs` [1, 6], `occs` fp32 [r^3] and
+`binaries` bool [1, r, r, r].  In the reference the grid never influences a rendered value.  Here it can: with
+`occ_grid=` an eonerf_code_amd.occupancy.OccupancyGrid, save_checkpoint writes that grid's real `occs` / `binaries` (the undilated
+bits) and load_checkpoint fills the grid from the file -- from a checkpoint of the reference's own trainer as well -- for export
+renders to cull by.  Without it the file carries the inert state it always has: zero `occs`, all-ones `binaries`, which is a valid
+grid that culls nothing."""
 import os
 
 import torch
@@ -43,9 +47,9 @@ def adam_state_dict(field, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), ep
     return {"state": state, "param_groups": [group]}
 
 
-def save_checkpoint(path, epoch, field, trainer=None, loss=None, grid_resolution=128):
+def save_checkpoint(path, epoch, field, trainer=None, loss=None, grid_resolution=128, occ_grid=None):
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    ckpt = {"epoch": epoch, "occ_grid_state_dict": occ_grid_state_dict(grid_resolution),
+    ckpt = {"epoch": epoch, "occ_grid_state_dict": occ_grid_state_dict(grid_resolution) if occ_grid is None else occ_grid.state_dict(),
             "model_state_dict": {k: v.detach().cpu() for k, v in field.state_dict().items()},
             "optimizer_state_dict": (adam_state_dict(field, trainer.exp_avg, trainer.exp_avg_sq, trainer.step_count, trainer.lr,
                                                      trainer.betas, trainer.eps) if trainer is not None else None),
@@ -54,10 +58,13 @@ def save_checkpoint(path, epoch, field, trainer=None, loss=None, grid_resolution
     return path
 
 
-def load_checkpoint(path, field, trainer=None, map_location="cpu"):
-    """Inverse of save_checkpoint; also loads checkpoints written by the reference's train_eonerf.py."""
+def load_checkpoint(path, field, trainer=None, map_location="cpu", occ_grid=None):
+    """Inverse of save_checkpoint; also loads checkpoints written by the reference's train_eonerf.py.  occ_grid: an OccupancyGrid
+    that receives the file's grid."""
     ckpt = torch.load(path, map_location=map_location, weights_only=False)
     field.load_state_dict(ckpt["model_state_dict"], strict=True)
+    if occ_grid is not None:
+        occ_grid.load_state_dict(ckpt["occ_grid_state_dict"])
     if trainer is not None and ckpt.get("optimizer_state_dict"):
         by_name = {name: (off, r, c) for name, off, r, c in field._layout}
         st = ckpt["optimizer_state_dict"]["state"]

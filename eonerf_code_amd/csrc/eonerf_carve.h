@@ -181,6 +181,26 @@ inline FieldWs carve_field(const CarveCfg& cfg, void* base, int p_cap) {
     return w;
 }
 
+// ---- eonerf_occ_update (include/eonerf_occ.h): the field workspace of ONE chunk of cells (at most OCC_CHUNK, whatever r is) followed by
+//      the reduction scratch: one fp64 partial per block of the fixed grid, then [mean (fp64), thr (fp32)] ----
+constexpr int OCC_CHUNK = 1 << 18;
+constexpr int OCC_SUM_BLOCKS = 256;
+inline long long occ_cells(int r) { return (long long)r * r * r; }
+inline int occ_chunk_cells(int r) { return (int)std::min<long long>(occ_cells(r), OCC_CHUNK); }
+struct OccWs { PassBuffers b; int p_cap; double* partial; double* result; size_t bytes; };
+inline OccWs carve_occ(const CarveCfg& cfg, void* base, int r) {
+    OccWs w;
+    w.p_cap = field_p_cap_of(occ_chunk_cells(r));
+    const FieldWs f = carve_field(cfg, base, w.p_cap);
+    w.b = f.b;
+    Carver c(base);
+    c.off = f.bytes - 256;      // (where carve_field's own allocator stopped)
+    w.partial = c.take<double>(OCC_SUM_BLOCKS);
+    w.result = c.take<double>(2);
+    w.bytes = c.off + 256;
+    return w;
+}
+
 struct FieldTrainWs { PassBuffers b; float* m_bott; int* queue; size_t bytes; };
 // autograd pair (eonerf_field_forward_train / eonerf_field_backward): saved slabs, input gradient, the GEMM's bottleneck factors and queue
 inline FieldTrainWs carve_field_train(const CarveCfg& cfg, void* base, int p_cap, bool full) {

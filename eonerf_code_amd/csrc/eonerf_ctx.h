@@ -69,6 +69,8 @@ struct eonerf_ctx {
     int* enc_colmap = nullptr;       // [64] device: encoding slot -> reference column (or -1)
     int* dev_status = nullptr;       // STICKY device status word (watchdog bits of the pipelined backward, bit 8: a remote rank's fault);
                                      // written by the kernels, gates eonerf_adam_step, read and cleared only by eonerf_device_status
+    // occupancy grid of the export renders (eonerf_set_occupancy, include/eonerf_occ.h): a BORROWED device bit field, or nullptr
+    const uint32_t* occ_bits = nullptr; int occ_r = 0;
     bool weights_set = false;
     bool dens_dirty = false;         // density-only streams are re-packed lazily (only the shadow pass reads them) ...
     bool dens_used = false;          // ... unless the cycle since the last re-pack used them: then they are re-packed with the others (one launch fewer per step)
@@ -146,6 +148,9 @@ inline MlpBwdArgs mlp_bwd_args(const eonerf_ctx* ctx, const PassBuffers& b, int 
 // eonerf_ctx.hip: (re)packs the fp32 master weights into the given streams; the density-only streams on their first use since the last re-pack
 int eo_pack(const eonerf_ctx* ctx, const std::vector<const DevStream*>& streams, const float* flat, hipStream_t st);
 int eo_ensure_density_streams(eonerf_ctx* ctx, const float* flat, hipStream_t st);
+// eonerf_render.hip: eonerf_sample_rays with an explicit occupancy grid (bits == nullptr: none) -- eonerf_occ_sample_rays
+int eo_sample_rays(eonerf_ctx* ctx, const float* rays, const float* zsteps, const float* u, int perturb, int n_rays, const uint32_t* bits, int r,
+                   int64_t* ray_indices, float* t_starts, float* t_ends, float* pts_per_ray, int* n_dev, void* ws, size_t ws_bytes, void* stream);
 // eonerf_render.hip: one MLP pass forwards; the weight gradients of up to two passes
 int eo_run_mlp_fwd(eonerf_ctx* ctx, const PassBuffers& b, const float* flat, int p_cap, bool full, int mode, hipStream_t st, int prof_id = -1, bool render_train = false);
 int eo_run_weight_gradients(eonerf_ctx* ctx, const float* flat, float* d_flat, const PassBuffers* full, const PassBuffers* dens, int p_cap, float* m_bott,

@@ -43,6 +43,9 @@ struct SampleArgs {
     // optional flattened outputs of satnerf_sampling (sat_rendering.py:82-84): ray_indices, t_starts, t_ends
     int64_t* o_ray; float *o_ts, *o_te;
     unsigned long long* digest;   // eonerf_presample: += the digest of every ray the emit kernel reads (zeroed by the caller), or nullptr
+    // occupancy grid (include/eonerf_occ.h) or nullptr: a cube-valid sample is kept iff its cell's bit is set or it is the LAST cube-valid
+    // sample of its ray.  nullptr launches the instances without a lookup (the kernels are instantiated per GRID)
+    const uint32_t* occ_bits; int occ_r;
 };
 
 struct ShadeArgs {

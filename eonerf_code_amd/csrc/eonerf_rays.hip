@@ -29,22 +29,8 @@ EO_DEV float zperturbed(const float* zsteps, float near, int i, float u, int ns)
     return __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), u));       // perturb_z_vals, :46-54
 }
 
-// ---- jitter source: caller-provided arrays (parity tests, torch.rand) or the in-kernel Philox4x32-10 stream -------------
-//      Philox (Salmon et al. 2011, the generator behind torch.rand on GPUs): counter = (ray, lane, draw, call), key = seed;
-//      one counter gives the lane's (up to four) jitters (samples lane + 64 k); 24 random bits -> [0, 1) fp32, as torch.rand.
-EO_DEV void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
-}
-EO_DEV void philox_u4(uint64_t seed, uint32_t ray, uint32_t lane, uint32_t draw, uint32_t call, float (&u)[4]) {
-    uint32_t c[4] = {ray, lane, draw, call};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { philox_round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) u[k] = (float)(c[k] >> 8) * 0x1p-24f;
-}
+// ---- jitter source: caller-provided arrays (parity tests, torch.rand) or the in-kernel Philox4x32-10 stream (philox_u4, eonerf_rays_dev.h):
+//      counter = (ray, lane, draw, call), key = seed; one counter gives the lane's (up to four) jitters (samples lane + 64 k)
 // jitters of samples lane + 64 k of draw `draw` (0 camera, 1 camera retry, 2 sun) of ray `ray`
 template <int SPL>
 EO_DEV void jitter(const SampleArgs& a, const float* u_arr, int draw, int ray, int lane, float (&u)[SPL]) {
@@ -94,6 +80,23 @@ template <int SPL> EO_DEV int count_valid(const RaySamples<SPL>& s) {
     return n;
 }
 
+// ---- occupancy culling (include/eonerf_occ.h): of the cube-valid samples of a ray keep those whose cell's bit is set, and the LAST
+//      cube-valid one whatever its cell says -- a ray has a sample exactly when it has one without the grid (the "resample if any ray
+//      is empty" decision is the same decision) and patch_last's 1e10 interval lands on the same sample.  The last slot follows from
+//      the ballots: the highest non-empty group, then 63 - clz.  Only cube-valid lanes look a bit up, with the clamped cell index
+template <int SPL>
+EO_DEV void cull_by_grid(RaySamples<SPL>& s, const uint32_t* bits, int r, int lane) {
+    int top = -1, last_lane = -1;
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        const unsigned long long m = __ballot(s.valid[k]);
+        if (m) { top = k; last_lane = 63 - __clzll(m); }
+    }
+#pragma unroll
+    for (int k = 0; k < SPL; ++k)
+        if (s.valid[k]) s.valid[k] = occ_bit(bits, r, s.x[k], s.y[k], s.z[k]) || (k == top && lane == last_lane);
+}
+
 struct RayGeom { float ox, oy, oz, dx, dy, dz, near; };
 
 // camera rays come from the [R,11] table; sun rays start at the rendered surface point and look at the sun
@@ -120,17 +123,19 @@ EO_DEV RayGeom ray_geom(const SampleArgs& a, int ray) {
 }
 
 // ---- kernel 1: count samples per ray (for both the first draw and the "retry" draw; k_scan decides which one counts) ----
-template <int SPL>
+template <int SPL, bool GRID>
 EO_DEV void count_ray(const SampleArgs& a, int ray, int lane, const RayGeom& g) {
     float u[SPL];
     jitter<SPL>(a, a.u, a.sun_pass ? 2 : 0, ray, lane, u);
-    const RaySamples<SPL> s = sample_ray<SPL>(a.zsteps, a.n_samples, a.perturb, u, g.near, g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, lane);
+    RaySamples<SPL> s = sample_ray<SPL>(a.zsteps, a.n_samples, a.perturb, u, g.near, g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, lane);
+    if constexpr (GRID) cull_by_grid<SPL>(s, a.occ_bits, a.occ_r, lane);
     const int cnt = count_valid(s);
     int cnt_retry = cnt;
     if (a.retry) {
         // the reference's retry passes near=None -> zeros (sat_rendering.py:262)
         jitter<SPL>(a, a.u_retry, 1, ray, lane, u);
-        const RaySamples<SPL> s2 = sample_ray<SPL>(a.zsteps, a.n_samples, a.perturb, u, 0.f, g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, lane);
+        RaySamples<SPL> s2 = sample_ray<SPL>(a.zsteps, a.n_samples, a.perturb, u, 0.f, g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, lane);
+        if constexpr (GRID) cull_by_grid<SPL>(s2, a.occ_bits, a.occ_r, lane);
         cnt_retry = count_valid(s2);
     }
     if (lane == 0) {
@@ -138,11 +143,11 @@ EO_DEV void count_ray(const SampleArgs& a, int ray, int lane, const RayGeom& g) 
         a.cnt_retry[ray] = cnt_retry;
     }
 }
-template <int SPL>
+template <int SPL, bool GRID>
 __global__ __launch_bounds__(256) void k_count(SampleArgs a) {
     const int lane = threadIdx.x & 63, ray = blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 6);
     if (ray >= a.n_rays) return;
-    count_ray<SPL>(a, ray, lane, ray_geom(a, ray));
+    count_ray<SPL, GRID>(a, ray, lane, ray_geom(a, ray));
 }
 
 // ---- kernel 2: exclusive scan of the chosen counts -> offsets[R+1]; n_pts; pts_per_ray (first draw) ---------
@@ -190,7 +195,7 @@ __global__ __launch_bounds__(1024) void k_scan(SampleArgs a) {
 // its own for a 4096-element scan -- and decides the "resample if any ray is empty" branch (sat_rendering.py:260-262) from the same pass;
 // block 0 leaves the totals (n_pts, offsets[R], the retry flag).
 constexpr int SCAN_FUSED_MAX_RAYS = 8192;
-template <int SPL, bool SCAN>
+template <int SPL, bool SCAN, bool GRID>
 __global__ __launch_bounds__(256) void k_emit(SampleArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ray = blockIdx.x * RAYS_PER_BLOCK + wave;
     bool retry_scan = false;
@@ -241,7 +246,8 @@ __global__ __launch_bounds__(256) void k_emit(SampleArgs a) {
     const bool retry = SCAN ? retry_scan : (a.retry && (*a.flags & 1));
     float u[SPL];
     jitter<SPL>(a, retry ? a.u_retry : a.u, retry ? 1 : (a.sun_pass ? 2 : 0), ray, lane, u);
-    const RaySamples<SPL> s = sample_ray<SPL>(a.zsteps, a.n_samples, a.perturb, u, retry ? 0.f : g.near, g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, lane);
+    RaySamples<SPL> s = sample_ray<SPL>(a.zsteps, a.n_samples, a.perturb, u, retry ? 0.f : g.near, g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, lane);
+    if constexpr (GRID) cull_by_grid<SPL>(s, a.occ_bits, a.occ_r, lane);
     unsigned long long m[SPL];
     int before[SPL], n = 0;
 #pragma unroll
@@ -300,7 +306,8 @@ __global__ __launch_bounds__(256) void k_shade_fwd(ShadeArgs a) {
     shade_ray(a, ray, a.ray_rec + (size_t)ray * RAY_REC);
 }
 
-template <int SPL>
+// GRID: the shadow-ray count (count_sun) culls by a.sun's occupancy grid
+template <int SPL, bool GRID>
 __global__ __launch_bounds__(256) void k_composite_fwd(CompositeArgs a) {
     const int lane = threadIdx.x & 63, ray = blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 6);
     if (ray >= a.n_rays) return;
@@ -379,7 +386,7 @@ __global__ __launch_bounds__(256) void k_composite_fwd(CompositeArgs a) {
         }
     }
     // the shadow ray of this ray starts at the surface point it has just rendered: count its samples here (acc[0] = depth on every lane)
-    if (a.count_sun) count_ray<SPL>(a.sun, ray, lane, sun_geom(a.rays + (size_t)ray * 11, acc[0]));
+    if (a.count_sun) count_ray<SPL, GRID>(a.sun, ray, lane, sun_geom(a.rays + (size_t)ray * 11, acc[0]));
 }
 
 // ---- caller-provided flattened samples (radiance_fields/eonerf.py:196-220: gather, mid points, last t_end := 1e10) ----
@@ -456,15 +463,20 @@ __global__ void k_soa3_to_aos(const float* soa, int p_pad, int n, float* aos) {
 
 hipError_t eo_launch_sampler(const SampleArgs& a, hipStream_t st, bool counted) {
     const int blocks = (a.n_rays + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK;
-    eo_dispatch_spl(a.n_samples, [&](auto spl) {
+    auto launch = [&](auto spl, auto grid) {
         constexpr int SPL = decltype(spl)::value;
-        if (!counted) hipLaunchKernelGGL(k_count<SPL>, dim3(blocks), dim3(256), 0, st, a);
+        constexpr bool GRID = decltype(grid)::value;
+        if (!counted) hipLaunchKernelGGL((k_count<SPL, GRID>), dim3(blocks), dim3(256), 0, st, a);
         if (a.n_rays <= SCAN_FUSED_MAX_RAYS) {      // the scan rides in the emit kernel
-            hipLaunchKernelGGL((k_emit<SPL, true>), dim3(blocks), dim3(256), 0, st, a);
+            hipLaunchKernelGGL((k_emit<SPL, true, GRID>), dim3(blocks), dim3(256), 0, st, a);
         } else {
             hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, a);
-            hipLaunchKernelGGL((k_emit<SPL, false>), dim3(blocks), dim3(256), 0, st, a);
+            hipLaunchKernelGGL((k_emit<SPL, false, GRID>), dim3(blocks), dim3(256), 0, st, a);
         }
+    };
+    // without a grid the instances are the ones without a lookup: nothing of the culling is compiled into them
+    eo_dispatch_spl(a.n_samples, [&](auto spl) {
+        if (a.occ_bits) launch(spl, std::true_type()); else launch(spl, std::false_type());
     });
     return hipGetLastError();
 }
@@ -487,8 +499,11 @@ hipError_t eo_launch_rendering_out(const RenderingOutArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 hipError_t eo_launch_composite_fwd(const CompositeArgs& a, hipStream_t st) {
+    const dim3 blocks((a.n_rays + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK);
     eo_dispatch_spl(a.n_samples, [&](auto spl) {
-        hipLaunchKernelGGL(k_composite_fwd<decltype(spl)::value>, dim3((a.n_rays + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK), dim3(256), 0, st, a);
+        constexpr int SPL = decltype(spl)::value;
+        if (a.count_sun && a.sun.occ_bits) hipLaunchKernelGGL((k_composite_fwd<SPL, true>), blocks, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_composite_fwd<SPL, false>), blocks, dim3(256), 0, st, a);
     });
     return hipGetLastError();
 }

@@ -33,6 +33,35 @@ EO_DEV float wave_suffix_scan(float v, int lane) {
     return v;
 }
 
+// ---- Philox4x32-10 (Salmon et al. 2011, the generator behind torch.rand on GPUs): counter = (ray, lane, draw, call), key = seed;
+//      24 random bits -> [0, 1) fp32, as torch.rand.  Draws 0 (camera), 1 (camera retry), 2 (sun): the sampler; 3: the occupancy
+//      grid's per-cell sample point (eonerf_occ.hip, counter = (cell, 0, 3, call))
+EO_DEV void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
+}
+EO_DEV void philox_u4(uint64_t seed, uint32_t ray, uint32_t lane, uint32_t draw, uint32_t call, float (&u)[4]) {
+    uint32_t c[4] = {ray, lane, draw, call};
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { philox_round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = (float)(c[k] >> 8) * 0x1p-24f;
+}
+
+// ---- occupancy grid (include/eonerf_occ.h): cell of a point, per axis min(r - 1, (int)(((x + 1) * 0.5f) * (float)r)) as three
+//      separately rounded fp32 operations; the clamps keep the index inside [0, r) whatever x holds (x + 1 == 2.0f at x = 1 - 2^-24;
+//      the lower clamp never acts on a cube-valid coordinate, |x| < 1) -----------------------------------------------------------
+EO_DEV int occ_axis(float x, int r) {
+    const int i = (int)__fmul_rn(__fmul_rn(__fadd_rn(x, 1.0f), 0.5f), (float)r);
+    return i < 0 ? 0 : (i > r - 1 ? r - 1 : i);
+}
+EO_DEV bool occ_bit(const uint32_t* bits, int r, float x, float y, float z) {
+    const uint32_t c = (uint32_t)((occ_axis(x, r) * r + occ_axis(y, r)) * r + occ_axis(z, r));      // < r^3 <= 2^24
+    return (bits[c >> 5] >> (c & 31)) & 1u;
+}
+
 // ---- ambient head for one ray, computed by the whole wave (radiance_fields/eonerf.py:132-139,163-164) ------
 struct AmbientRay { float out[3]; float hid[2]; float pre[3]; float enc[27]; };
 

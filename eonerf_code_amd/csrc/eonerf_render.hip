@@ -195,6 +195,13 @@ int eonerf_set_noise_seed(eonerf_ctx* ctx, uint64_t seed) {
 int eonerf_sample_rays(eonerf_ctx* ctx, const float* rays, const float* zsteps, const float* u, int perturb, int n_rays,
                        int64_t* ray_indices, float* t_starts, float* t_ends, float* pts_per_ray, int* n_dev,
                        void* ws, size_t ws_bytes, void* stream) {
+    return eo_sample_rays(ctx, rays, zsteps, u, perturb, n_rays, nullptr, 0, ray_indices, t_starts, t_ends, pts_per_ray, n_dev, ws, ws_bytes, stream);
+}
+
+}  // extern "C"
+
+int eo_sample_rays(eonerf_ctx* ctx, const float* rays, const float* zsteps, const float* u, int perturb, int n_rays, const uint32_t* bits, int r,
+                   int64_t* ray_indices, float* t_starts, float* t_ends, float* pts_per_ray, int* n_dev, void* ws, size_t ws_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (n_rays == 0) return EONERF_OK;
     if (!ctx || !rays || !zsteps || !ray_indices || !t_starts || !t_ends || n_rays < 0 || !ws) return EONERF_E_ARG;
@@ -210,11 +217,14 @@ int eonerf_sample_rays(eonerf_ctx* ctx, const float* rays, const float* zsteps, 
     sa.flags = w.flags; sa.n_pts = w.cam.n_pts;
     sa.px = w.cam.px; sa.py = w.cam.py; sa.pz = w.cam.pz; sa.tmid = w.cam.tmid; sa.delta = w.cam.delta; sa.simg = w.cam.simg;
     sa.o_ray = ray_indices; sa.o_ts = t_starts; sa.o_te = t_ends;
+    sa.occ_bits = bits; sa.occ_r = bits ? r : 0;
     HIP_TRY(eo_launch_sampler(sa, st));
     if (n_dev) HIP_TRY(hipMemcpyAsync(n_dev, w.cam.n_pts, sizeof(int), hipMemcpyDeviceToDevice, st));
     if (pts_per_ray) HIP_TRY(eo_launch_int_to_float(w.cam.counts, n_rays, pts_per_ray, st));
     return EONERF_OK;
 }
+
+extern "C" {
 
 // EONerfMLP.rendering / render_depth on the caller's flattened samples.  train: under autograd (radiance_fields/eonerf.py:172-248) -- the
 // same kernels with the training-mode forward chain (activations, masks and the compositing inputs stay in the workspace for
@@ -340,7 +350,7 @@ int eonerf_render_forward(eonerf_ctx* ctx, const float* flat, const float* rays,
                             pre.count_out == n_samples_dev && pre.n_rays == n_rays && pre.flags == flags && pre.n_samples == ctx->n_samples && pre.pipe == ctx->pipe;
     ctx->pre.valid = false;      // consumed, or dropped: this call's kernels write the workspace the record described (or the caller moved on)
     ctx->pre_consumed_ws = (presampled && train) ? ws : nullptr;
-    SampleArgs sa = camera_sample_args(ctx, w, rays, img_idx, zsteps, u_cam, u_retry, n_rays, n_samples_dev);
+    SampleArgs sa = camera_sample_args(ctx, w, rays, img_idx, zsteps, u_cam, u_retry, n_rays, n_samples_dev, !train);      // (a training forward never culls)
     if (presampled) sa.call = pre.call;                       // (the shadow pass draws under the same call number)
     else {
         if (philox) sa.call = ctx->noise_call++;

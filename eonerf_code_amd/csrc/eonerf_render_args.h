@@ -17,9 +17,10 @@ inline CompositeArgs composite_args(const eonerf_ctx* ctx, const RenderWs& w, co
 }
 
 // Arguments of the camera pass's sampler launch (eonerf_render_forward, eonerf_presample, eonerf_render_sun_sweep); the Philox call
-// number is the caller's
+// number is the caller's.  cull: the call honours the context's occupancy grid (include/eonerf_occ.h: inference forwards and the sun
+// sweep; never a training forward or eonerf_presample) -- sun_sample_args inherits it, so the shadow pass culls by the same grid
 inline SampleArgs camera_sample_args(const eonerf_ctx* ctx, const RenderWs& w, const float* rays, const int64_t* img_idx, const float* zsteps,
-                                     const float* u_cam, const float* u_retry, int n_rays, int* n_samples_dev) {
+                                     const float* u_cam, const float* u_retry, int n_rays, int* n_samples_dev, bool cull = false) {
     SampleArgs sa;
     memset(&sa, 0, sizeof(sa));
     sa.n_samples = ctx->n_samples;
@@ -30,6 +31,7 @@ inline SampleArgs camera_sample_args(const eonerf_ctx* ctx, const RenderWs& w, c
     sa.cnt_first = w.cnt_first; sa.cnt_retry = w.cnt_retry; sa.counts = w.cam.counts; sa.offsets = w.cam.offsets;
     sa.flags = w.flags; sa.n_pts = w.cam.n_pts; sa.n_pts_copy = n_samples_dev;       // the scan kernel also fills the caller's count
     sa.px = w.cam.px; sa.py = w.cam.py; sa.pz = w.cam.pz; sa.tmid = w.cam.tmid; sa.delta = w.cam.delta; sa.simg = w.cam.simg;
+    if (cull && ctx->occ_bits) { sa.occ_bits = ctx->occ_bits; sa.occ_r = ctx->occ_r; }
     return sa;
 }
 

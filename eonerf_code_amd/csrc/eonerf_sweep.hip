@@ -47,7 +47,7 @@ int eonerf_render_sun_sweep(eonerf_ctx* ctx, const float* flat, const float* ray
     ctx->pre.valid = false;      // dropped: this call's kernels write the workspace the record described (or the caller moved on)
 
     // ---- camera pass, once: sample -> field.  Its sampler reads columns 0..6 of the table only ----------------
-    SampleArgs sa = camera_sample_args(ctx, w, rays, img_idx, zsteps, u_cam, u_retry, n_rays, n_samples_dev);
+    SampleArgs sa = camera_sample_args(ctx, w, rays, img_idx, zsteps, u_cam, u_retry, n_rays, n_samples_dev, true);      // (honours the context's occupancy grid)
     if (philox) sa.call = ctx->noise_call++;      // the ONE call number of the sweep: every shadow pass draws under it
     HIP_TRY(eo_launch_sampler(sa, st));
     int rc = eo_run_mlp_fwd(ctx, w.cam, flat, p_cap, true, 0, st, EONERF_PROF_FWD_CHAIN_CAMERA, false);

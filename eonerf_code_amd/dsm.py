@@ -148,7 +148,7 @@ def dsm_mae(gt, sec, transform, water=None, return_err=False):
 
 
 def evaluate_dsm(field, gt, roi, scene_offset, scene_scale, sun, chunk=5120, render_step_size=None, water=None, scaling=False,
-                 h=None, w=None, noise=None, return_all=False):
+                 h=None, w=None, noise=None, return_all=False, occupancy_grid=None):
     """Validation DSM MAE of a field against a lidar DSM, as train_eonerf.py:197-282 / eval_eonerf.py:286-324 obtain it:
     nadir rays (h x w, default the GT's size) -> render_image(only_depth=True) in the field's export precision -> raster on the GT's
     grid (roi = x, y, size, res) -> water mask -> registration -> MAE.
@@ -167,7 +167,7 @@ def evaluate_dsm(field, gt, roi, scene_offset, scene_scale, sun, chunk=5120, ren
         if int(2 / render_step_size) < field._n_samples:
             render_step_size = math.nextafter(render_step_size, 0.0)
     with torch.no_grad():
-        res, _ = render_image(field, None, define_satrays_from_tensors(rays, ts), None, None, epoch_idx=None, chunk=chunk,
+        res, _ = render_image(field, occupancy_grid, define_satrays_from_tensors(rays, ts), None, None, epoch_idx=None, chunk=chunk,
                               render_step_size=render_step_size, only_depth=True, eval=True, noise=noise)
     depth = res["depth"].reshape(-1)
     dsm = rasterize_dsm(rays, depth, scene_offset, scene_scale, roi=roi)

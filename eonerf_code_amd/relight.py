@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from .datasets.satellite import SatRays, namedtuple_map, satrays_to_table, sun_direction
+from .occupancy import OccupancyGrid, grid_on
 from .radiance_fields.eonerf import _ptr, _stream
 from .sat_rendering import RESULT_SLICES, _zsteps, n_samples_of
 
@@ -36,13 +37,17 @@ def sun_table(sun_elevation_deg, sun_azimuth_deg, scene_scale, device="cuda"):
 
 
 def render_sun_sweep(radiance_field, rays: SatRays, suns, chunk: int = 5120, render_step_size: float = 1e-3, eval: bool = False,
-                     keys=("rgb", "geo_shadows"), noise=None):
+                     keys=("rgb", "geo_shadows"), noise=None, occupancy_grid=None):
     """Render the pixels of a view under K sun directions.  suns: [K,3] as sun_table gives them (rays.sundirs is not read).
     Always an export render: under no_grad, on the module's export context (EONerfMLP.eval_precision), with render_image's
     protocol -- one host sync for the sample count, then the fp16x3 range check, and once more on the fp32 export context if it
     fired.  Returns (results, n_rendering_samples): results[key] is [K, *lead, c] for the keys that depend on the sun (SUN_KEYS)
     and [*lead, c] for all others, lead = the rays' leading shape.  Only the requested keys are kept.
-    noise: per chunk (u_cam [c,S], u_retry [c,S] or None, u_sun [K,c,S]), or None: the sampler kernels draw the jitter."""
+    noise: per chunk (u_cam [c,S], u_retry [c,S] or None, u_sun [K,c,S]), or None: the sampler kernels draw the jitter.
+    occupancy_grid: an OccupancyGrid the camera pass and every shadow pass cull by (None or any other object: no culling)."""
+    grid = occupancy_grid if isinstance(occupancy_grid, OccupancyGrid) else None
+    if grid is not None:
+        grid.check_step_size(render_step_size)
     slices = {k: (a, b) for k, a, b in RESULT_SLICES}
     keys = tuple(keys)
     for k in keys:
@@ -85,9 +90,10 @@ def render_sun_sweep(radiance_field, rays: SatRays, suns, chunk: int = 5120, ren
                 nb = L.eonerf_sun_sweep_workspace_bytes(native, n, n_suns)
                 ws = radiance_field._workspace("render", nb)
                 out = buf[:n_suns * n * 21].view(n_suns, n, 21)
-                _lib.check(L.eonerf_render_sun_sweep(native, _ptr(flat), _ptr(table[i:i + n]), _ptr(img[i:i + n]), _ptr(_zsteps(dev, ns)),
-                                                     _ptr(u_cam), _ptr(u_retry), _ptr(u_sun), _ptr(suns), n_suns, n, flags, _ptr(out),
-                                                     _ptr(counts[j:j + 1]), _ptr(ws), ws.numel(), _stream()))
+                with grid_on(native, grid):
+                    _lib.check(L.eonerf_render_sun_sweep(native, _ptr(flat), _ptr(table[i:i + n]), _ptr(img[i:i + n]), _ptr(_zsteps(dev, ns)),
+                                                         _ptr(u_cam), _ptr(u_retry), _ptr(u_sun), _ptr(suns), n_suns, n, flags, _ptr(out),
+                                                         _ptr(counts[j:j + 1]), _ptr(ws), ws.numel(), _stream()))
                 for k in keys:
                     a, b = slices[k]
                     if k in SUN_KEYS:

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .datasets.satellite import SatRays, namedtuple_map, satrays_to_table
+from .occupancy import OccupancyGrid, grid_on
 from .radiance_fields.eonerf import _ptr, _stream
 
 RESULT_SLICES = (("rgb", 0, 3), ("depth", 3, 4), ("albedo_rgb", 4, 7), ("ambient_rgb", 7, 10), ("geo_shadows", 10, 11),
@@ -91,7 +92,7 @@ class _RenderChunk(torch.autograd.Function):
     """One chunk of render_image as a differentiable op; the parameters are inputs so autograd routes their grads."""
 
     @staticmethod
-    def forward(ctx, field, table, img, flags, export, u_cam, u_retry, u_sun, *params):
+    def forward(ctx, field, table, img, flags, export, u_cam, u_retry, u_sun, grid, *params):
         L = _lib.lib()
         train = bool(flags & _lib.F_TRAIN)
         native, flat = field._native(export and not train)      # export renders of a bf16 field: its fp32 context (EONerfMLP.eval_precision)
@@ -102,9 +103,12 @@ class _RenderChunk(torch.autograd.Function):
         ws = torch.empty(nb, dtype=torch.uint8, device=table.device) if train else field._workspace("render", nb)
         out = torch.empty(n, 21, dtype=torch.float32, device=table.device)
         n_samples = torch.zeros(1, dtype=torch.int32, device=table.device)
-        _lib.check(L.eonerf_render_forward(native, _ptr(flat), _ptr(table), _ptr(img), _ptr(_zsteps(table.device, ns)),
-                                           _ptr(u_cam), _ptr(u_retry), _ptr(u_sun), n, flags, _ptr(out), _ptr(n_samples),
-                                           _ptr(ws), ws.numel(), _stream()))
+        # grid: an OccupancyGrid the call culls by (export renders only: render_rays_chunk passes None otherwise), set on the context
+        # this very call runs on -- the fp32 context of the range retry included -- and cleared behind it
+        with grid_on(native, grid):
+            _lib.check(L.eonerf_render_forward(native, _ptr(flat), _ptr(table), _ptr(img), _ptr(_zsteps(table.device, ns)),
+                                               _ptr(u_cam), _ptr(u_retry), _ptr(u_sun), n, flags, _ptr(out), _ptr(n_samples),
+                                               _ptr(ws), ws.numel(), _stream()))
         if train:
             ctx.field, ctx.flags, ctx.ws, ctx.ns = field, flags, ws, ns
             ctx.save_for_backward(table, img)
@@ -125,11 +129,12 @@ class _RenderChunk(torch.autograd.Function):
         _lib.check(L.eonerf_render_backward(field._ctx, _ptr(flat), _ptr(table), _ptr(img), table.shape[0], flags,
                                             _ptr(d_out), _ptr(d_flat), _ptr(ws), ws.numel(), _stream()))
         ctx.ws = None
-        return (None,) * 8 + tuple(field.grad_views(d_flat))
+        return (None,) * 9 + tuple(field.grad_views(d_flat))
 
 
-def render_rays_chunk(radiance_field, table, img, epoch_idx, eval=False, only_depth=False, noise=None):
-    """table [n,11] fp32, img [n] int64 -> (out [n,21], n_samples int32[1]) for one chunk."""
+def render_rays_chunk(radiance_field, table, img, epoch_idx, eval=False, only_depth=False, noise=None, occupancy_grid=None):
+    """table [n,11] fp32, img [n] int64 -> (out [n,21], n_samples int32[1]) for one chunk.  occupancy_grid: an OccupancyGrid an
+    EXPORT chunk culls by; a training chunk, a non-export chunk and any other object ignore it."""
     # an EXPORT render: eval=True (eval_eonerf.py:311-324) or a module in .eval() mode outside autograd (train_eonerf.py:197-226)
     export = bool(eval) or (not radiance_field.training and not torch.is_grad_enabled())
     n, dev = table.shape[0], table.device
@@ -147,7 +152,8 @@ def render_rays_chunk(radiance_field, table, img, epoch_idx, eval=False, only_de
         u_cam = u_retry = u_sun = None
     else:
         u_cam, u_retry, u_sun = (None if t is None else t.to(dev, torch.float32).contiguous() for t in noise)
-    return _RenderChunk.apply(radiance_field, table, img, flags, export, u_cam, u_retry, u_sun, *params)
+    grid = occupancy_grid if (isinstance(occupancy_grid, OccupancyGrid) and export and not flags & _lib.F_TRAIN) else None
+    return _RenderChunk.apply(radiance_field, table, img, flags, export, u_cam, u_retry, u_sun, grid, *params)
 
 
 def render_image(
@@ -172,9 +178,14 @@ def render_image(
     eval: bool = False,
     noise=None,
 ):
-    """Render the pixels of an image (sat_rendering.py:176-335).  Returns (results dict, n_rendering_samples)."""
+    """Render the pixels of an image (sat_rendering.py:176-335).  Returns (results dict, n_rendering_samples).
+    occupancy_grid: an eonerf_code_amd.occupancy.OccupancyGrid makes an EXPORT render (eval=True, or a module in .eval() mode under
+    no_grad) skip the samples of empty cells -- pts_per_ray / sc_pts_per_ray and n_rendering_samples then count the kept samples; a
+    training call, and None or any other object (the reference passes its never-sampled nerfacc estimator), ignore it."""
     radiance_field._context()
     radiance_field.set_n_samples(n_samples_of(render_step_size))
+    if isinstance(occupancy_grid, OccupancyGrid):
+        occupancy_grid.check_step_size(render_step_size)
     rays_shape = rays.origins.shape
     if len(rays_shape) == 3:
         height, width, _ = rays_shape
@@ -190,7 +201,7 @@ def render_image(
         for k, i in enumerate(range(0, num_rays, chunk)):
             nz = None if noise is None else noise[k]
             out, n = render_rays_chunk(radiance_field, table[i:i + chunk], img[i:i + chunk], epoch_idx, eval=eval,
-                                       only_depth=only_depth, noise=nz)
+                                       only_depth=only_depth, noise=nz, occupancy_grid=occupancy_grid)
             outs.append(out)
             counts.append(n)
         out = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]

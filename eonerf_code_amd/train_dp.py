@@ -21,6 +21,11 @@ priors of the whole table on its own device at start-up (eonerf_code_amd.priors.
 on every rank), carries them as a RayTable extra and adds metrics.depth_loss_L2 with weight --w_depth, multiplied by 0.8 after every
 epoch (train_eonerf.py:94,145-149,305-306); the status line gains train/depth_l2 and depth_weight.  Each rank takes the masked mean
 over its own rays.  Without it nothing changes.
+
+`--occ_grid` mirrors the reference's occupancy grid (train_eonerf.py:74,112-119): rank 0 updates a 128^3 grid from the field's density
+every `--occ_every` steps on the training context (eonerf_code_amd.occupancy.OccupancyGrid), the per-epoch validation renders
+(`--gt_dsm`, `--val_images`) skip the samples of its empty cells (the grid dilated by one cell), and checkpoints carry it.  The training
+step itself never reads the grid.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -62,6 +67,8 @@ def main():
     ap.add_argument("--val_max", type=int, default=5, help="validation images rendered per epoch (train_eonerf.py:200)")
     ap.add_argument("--init_dsm", default=None, help="torch file with an initial DSM, its bounds / UTM zone, the scene normalisation and the images' RPCs: depth supervision")
     ap.add_argument("--w_depth", type=float, default=100.0, help="weight of the depth term (x 0.8 after every epoch)")
+    ap.add_argument("--occ_grid", action="store_true", help="keep an occupancy grid (rank 0): validation renders cull by it, checkpoints carry it")
+    ap.add_argument("--occ_every", type=int, default=50, help="steps between occupancy grid updates (train_eonerf.py:112-119)")
     args = ap.parse_args()
 
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -110,6 +117,10 @@ def main():
     trainer = FusedTrainer(field, lr=args.lr, max_rays=args.batch_size, keep_message=False, n_samples=args.n_samples)
     trainer.set_noise_seed(42 + 1000003 * rank)                              # per-rank jitter stream
     steps_per_epoch = max(1, table.steps_per_epoch(args.batch_size))
+    occ = None
+    if args.occ_grid and rank == 0:
+        from .occupancy import OccupancyGrid
+        occ = OccupancyGrid(128, device=dev)                                   # opt.py:86
     gt = None
     if args.gt_dsm:
         gt = torch.load(args.gt_dsm, map_location="cpu")
@@ -145,6 +156,8 @@ def main():
                 r2, im2, _ = table.batch(epoch, i + 1, args.batch_size)
                 nxt = (r2, im2, epoch) if extras is None else (r2, im2, epoch, True)
             loss = trainer.step(r, im, px, epoch, next_batch=nxt, aux_loss=aux)
+            if occ is not None:                                             # train_eonerf.py:112-119 (no host sync)
+                occ.update_every_n_steps(step, field, 2.0 / args.n_samples, n=args.occ_every)
             if step % args.check_every == 0:                                # the only host sync, every 1000 steps (:173-178)
                 # on EVERY rank: raises (-> non-zero exit of the job) if a device-side hand-off timed out on ANY rank since the last
                 # check; the fault flag of the gradient message has kept all replicas from applying an update since
@@ -160,7 +173,7 @@ def main():
                 # while the host's step count keeps running -- every rank checks (and raises together) BEFORE rank 0 writes
                 trainer.check_device_status()
             if save_now and rank == 0:
-                save_checkpoint(os.path.join(args.logs_dir, args.exp_name, f"ckpts/epoch={epoch}.ckpt"), epoch, field, trainer, loss)
+                save_checkpoint(os.path.join(args.logs_dir, args.exp_name, f"ckpts/epoch={epoch}.ckpt"), epoch, field, trainer, loss, occ_grid=occ)
             if step == args.max_train_steps:
                 trainer.check_device_status()
                 if args.dump_params:                                        # replica-equality checks of the tests
@@ -175,7 +188,7 @@ def main():
                 from .dsm import evaluate_dsm
                 sun = [float(x) for x in gt.get("sun", (0.0, 0.0))]
                 mae = evaluate_dsm(field, gt["dsm"], [float(x) for x in gt["roi"]], gt["scene_offset"], gt["scene_scale"], sun,
-                                   chunk=args.val_chunk, water=gt["water"])
+                                   chunk=args.val_chunk, water=gt["water"], occupancy_grid=occ)
                 mae, n_valid = mae.tolist()                                 # the validation's one read-back
                 print(f"epoch={epoch} | elapsed_time={time.time() - tic:.2f}s | step={step} | val/mae={mae:.4f} | val/cells={int(n_valid)}", flush=True)
         if args.val_images:                                                 # the held-out images of the same block (:199-294)
@@ -183,7 +196,7 @@ def main():
                 trainer.check_device_status()                               # on every rank (with --gt_dsm the check above has just run)
             if rank == 0 and val_images:
                 from .validation import validate_images
-                _, means = validate_images(field, val_images, epoch, chunk=args.val_chunk, gt=gt, max_images=args.val_max)
+                _, means = validate_images(field, val_images, epoch, chunk=args.val_chunk, gt=gt, max_images=args.val_max, occupancy_grid=occ)
                 names = ("loss", "coarse_color", "coarse_logbeta", "psnr") + (("mae",) if gt is not None else ())
                 vals = torch.stack([means[k] for k in names]).tolist()      # the validation's one read-back
                 line = (f"epoch={epoch} | elapsed_time={time.time() - tic:.2f}s | step={step} | val/loss={vals[0]:.5f} | "
