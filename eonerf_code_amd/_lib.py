@@ -38,6 +38,8 @@ SWEEP_SYMBOLS = ["eonerf_sweep_version", "eonerf_sun_sweep_workspace_bytes", "eo
 # include/eonerf_occ.h: the occupancy grid (occupancy.py) -- update, dilation, the grid of a context's export renders, the pinned sampler
 OCC_SYMBOLS = ["eonerf_occ_version", "eonerf_occ_workspace_bytes", "eonerf_occ_update", "eonerf_occ_dilate", "eonerf_set_occupancy",
                "eonerf_occ_sample_rays"]
+# include/eonerf_march.h: block-wise early ray termination of export renders (sat_rendering.render_image(early_stop_eps=...))
+MARCH_SYMBOLS = ["eonerf_march_version", "eonerf_march_workspace_bytes", "eonerf_render_forward_march", "eonerf_march_sample_round"]
 
 
 class EonerfRpc(C.Structure):
@@ -63,6 +65,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_metrics.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_sweep.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_occ.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_march.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -187,7 +190,12 @@ def lib():
     L.eonerf_occ_dilate.argtypes = [vp, vp, i, vp]
     L.eonerf_set_occupancy.argtypes = [vp, vp, i]
     L.eonerf_occ_sample_rays.argtypes = [vp, vp, vp, vp, i, i, vp, i, vp, vp, vp, vp, vp, vp, sz, vp]
-    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS:
+    L.eonerf_march_version.restype = i
+    L.eonerf_march_workspace_bytes.restype = sz
+    L.eonerf_march_workspace_bytes.argtypes = [vp, i, i, i]
+    L.eonerf_render_forward_march.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, fp, i, vp, vp, vp, vp, sz, vp]
+    L.eonerf_march_sample_round.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, sz, vp]
+    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS:
         getattr(L, name)
     _lib = L
     return L

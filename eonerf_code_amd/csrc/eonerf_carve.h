@@ -159,6 +159,45 @@ inline SweepWs carve_sweep(const CarveCfg& cfg, void* base, int n_rays) {
     return s;
 }
 
+// ---- eonerf_render_forward_march (include/eonerf_march.h): a layout of its own.  Per-ray sampler results and march state, then the
+//      buffers of ONE round of ONE pass -- n_rays x block sample slots, shared by the camera and the shadow pass ----
+inline bool march_block_ok(int block) { return block == 16 || block == 32 || block == 64; }
+inline int march_p_cap_of(int n_rays, int block) { return round_up(std::max(n_rays, 1) * block, 256); }
+inline int march_rounds(int n_samples, int block) { return (n_samples - 1 + block - 1) / block; }
+constexpr int MARCH_ACC = 8;      // per-ray sums carried between rounds: depth, albedo3, ts, tb, wsum (+ one spare float)
+struct MarchWs {
+    int *cnt_first, *cnt_retry, *last_first, *last_retry, *win_first, *win_retry, *flags;      // camera pass: full counts, last valid slot, window count per draw
+    int *sun_cnt, *sun_last, *sun_win;                                                         // shadow pass (one draw)
+    int *alive, *kept_cam, *kept_sun; float *od, *acc;                                         // march state; acc [R][MARCH_ACC]
+    float* ray_rec;
+    PassBuffers round; int p_cap;
+    size_t bytes;
+};
+inline MarchWs carve_march(const CarveCfg& cfg, void* base, int n_rays, int flags, int block) {
+    Carver c(base);
+    MarchWs w;
+    const bool od = flags & EONERF_F_ONLY_DEPTH;
+    w.cnt_first = c.take<int>(n_rays); w.cnt_retry = c.take<int>(n_rays); w.last_first = c.take<int>(n_rays); w.last_retry = c.take<int>(n_rays);
+    w.win_first = c.take<int>(n_rays); w.win_retry = c.take<int>(n_rays); w.flags = c.take<int>(4);
+    w.sun_cnt = c.take<int>(n_rays); w.sun_last = c.take<int>(n_rays); w.sun_win = c.take<int>(n_rays);
+    w.alive = c.take<int>(n_rays); w.kept_cam = c.take<int>(n_rays); w.kept_sun = c.take<int>(n_rays);
+    w.od = c.take<float>(n_rays); w.acc = c.take<float>((size_t)n_rays * MARCH_ACC);
+    w.ray_rec = c.take<float>((size_t)n_rays * RAY_REC);
+    w.p_cap = march_p_cap_of(n_rays, block);
+    carve_pass(c, w.round, n_rays, w.p_cap, !od, false, false, cfg.bf16 ? 2 : 4);
+    w.bytes = c.off + 256;
+    return w;
+}
+// The ONE decision whether a march call is refused on its own arguments, in the documented order (include/eonerf_march.h); `need` =
+// carve_march(...).bytes, only looked at when the block size is a legal one
+inline int march_refusal(int flags, float early_stop_eps, int block, size_t ws_bytes, size_t need) {
+    if (flags & EONERF_F_TRAIN) return EONERF_E_UNSUPPORTED;
+    if (!(early_stop_eps >= 0.0f && early_stop_eps < 1.0f)) return EONERF_E_ARG;      // (NaN fails both comparisons)
+    if (!march_block_ok(block)) return EONERF_E_ARG;
+    if (ws_bytes < need) return EONERF_E_WORKSPACE;
+    return EONERF_OK;
+}
+
 // Everything a pipelined backward call needs zeroed, as ONE span: [bottleneck factors | GEMM work queue | the PIPE_LAUNCHES sync blocks].
 // Cleared by the call's first kernel (ShadeBwdArgs::zero_base) or by the memset in front of its first pipelined launch
 struct ZeroSpan { uint8_t* base; size_t bytes; };

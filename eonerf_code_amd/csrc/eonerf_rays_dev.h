@@ -62,6 +62,119 @@ EO_DEV bool occ_bit(const uint32_t* bits, int r, float x, float y, float z) {
     return (bits[c >> 5] >> (c & 31)) & 1u;
 }
 
+// ---- the SatNeRF sampler for one ray (sat_rendering.py:46-84), evaluated without FMA contraction so that
+//      t values and the cube-filter decisions are bit-identical to the reference's fp32 torch ops ------------
+template <int SPL> struct RaySamples {
+    float ts[SPL], te[SPL], mid[SPL], x[SPL], y[SPL], z[SPL];
+    bool valid[SPL];
+};
+
+EO_DEV float zval(const float* zsteps, float near, int i) {
+    // near * (1 - s) + (near + 2) * s      (sat_rendering.py:60-68)
+    const float s = zsteps[i];
+    return __fadd_rn(__fmul_rn(near, __fsub_rn(1.0f, s)), __fmul_rn(__fadd_rn(near, 2.0f), s));
+}
+// ns = n_samples = int(2 / render_step_size) (sat_rendering.py:64); zsteps = linspace(0, 1, ns)
+EO_DEV float zperturbed(const float* zsteps, float near, int i, float u, int ns) {
+    const float zi = zval(zsteps, near, i);
+    const float lower = i == 0 ? zi : __fmul_rn(0.5f, __fadd_rn(zval(zsteps, near, i - 1), zi));
+    const float upper = i == ns - 1 ? zi : __fmul_rn(0.5f, __fadd_rn(zi, zval(zsteps, near, i + 1)));
+    return __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), u));       // perturb_z_vals, :46-54
+}
+
+// ---- jitter source: caller-provided arrays (parity tests, torch.rand) or the in-kernel Philox4x32-10 stream (philox_u4, eonerf_rays_dev.h):
+//      counter = (ray, lane, draw, call), key = seed; one counter gives the lane's (up to four) jitters (samples lane + 64 k)
+// jitters of samples lane + 64 k of draw `draw` (0 camera, 1 camera retry, 2 sun) of ray `ray`
+template <int SPL>
+EO_DEV void jitter(const SampleArgs& a, const float* u_arr, int draw, int ray, int lane, float (&u)[SPL]) {
+    if (u_arr) {
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) u[k] = lane + 64 * k < a.n_samples ? u_arr[(size_t)ray * a.n_samples + lane + 64 * k] : 0.f;      // [R][n_samples]
+    } else {
+        float u4[4];
+        philox_u4(a.seed, (uint32_t)ray, (uint32_t)lane, (uint32_t)draw, a.call, u4);
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) u[k] = u4[k];
+    }
+}
+
+template <int SPL>
+EO_DEV RaySamples<SPL> sample_ray(const float* zsteps, int ns, bool perturb, const float (&u)[SPL], float near, float ox, float oy, float oz,
+                                  float dx, float dy, float dz, int lane) {
+    RaySamples<SPL> s;
+    float zs[SPL], zn[SPL];
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {      // perturb=False: :70-71 skipped.  Slots beyond the last z value repeat it (never used: masked below)
+        const int i = lane + 64 * k < ns ? lane + 64 * k : ns - 1;
+        zs[k] = perturb ? zperturbed(zsteps, near, i, u[k], ns) : zval(zsteps, near, i);
+    }
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        zn[k] = __shfl_down(zs[k], 1, 64);
+        if (k + 1 < SPL) { const float z0 = __shfl(zs[k + 1 < SPL ? k + 1 : k], 0, 64); if (lane == 63) zn[k] = z0; }      // (last group, lane 63: interval NS - 1 does not exist)
+    }
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        s.ts[k] = zs[k];
+        s.te[k] = __fadd_rn(zs[k], __fsub_rn(zn[k], zs[k]));               // a + (b - a), :74
+        s.mid[k] = __fdiv_rn(__fadd_rn(s.ts[k], s.te[k]), 2.0f);           // :79
+        s.x[k] = __fadd_rn(ox, __fmul_rn(dx, s.mid[k]));                    // :80
+        s.y[k] = __fadd_rn(oy, __fmul_rn(dy, s.mid[k]));
+        s.z[k] = __fadd_rn(oz, __fmul_rn(dz, s.mid[k]));
+        const bool inside = fabsf(s.x[k]) < 1.0f && fabsf(s.y[k]) < 1.0f && fabsf(s.z[k]) < 1.0f;   // :18-22
+        s.valid[k] = inside && lane + 64 * k < ns - 1;      // interval i = [z_i, z_{i+1}], i < n_samples - 1 (:74-76)
+    }
+    return s;
+}
+template <int SPL> EO_DEV int count_valid(const RaySamples<SPL>& s) {
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) n += __popcll(__ballot(s.valid[k]));
+    return n;
+}
+
+// ---- occupancy culling (include/eonerf_occ.h): of the cube-valid samples of a ray keep those whose cell's bit is set, and the LAST
+//      cube-valid one whatever its cell says -- a ray has a sample exactly when it has one without the grid (the "resample if any ray
+//      is empty" decision is the same decision) and patch_last's 1e10 interval lands on the same sample.  The last slot follows from
+//      the ballots: the highest non-empty group, then 63 - clz.  Only cube-valid lanes look a bit up, with the clamped cell index
+template <int SPL>
+EO_DEV void cull_by_grid(RaySamples<SPL>& s, const uint32_t* bits, int r, int lane) {
+    int top = -1, last_lane = -1;
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        const unsigned long long m = __ballot(s.valid[k]);
+        if (m) { top = k; last_lane = 63 - __clzll(m); }
+    }
+#pragma unroll
+    for (int k = 0; k < SPL; ++k)
+        if (s.valid[k]) s.valid[k] = occ_bit(bits, r, s.x[k], s.y[k], s.z[k]) || (k == top && lane == last_lane);
+}
+
+struct RayGeom { float ox, oy, oz, dx, dy, dz, near; };
+
+// camera rays come from the [R,11] table; sun rays start at the rendered surface point and look at the sun
+// (sat_rendering.py:90-91: origin = o + depth*d, dir = -sundir, near = 0)
+EO_DEV RayGeom sun_geom(const float* r, float depth) {
+    RayGeom g;
+    g.ox = __fadd_rn(r[0], __fmul_rn(depth, r[3]));
+    g.oy = __fadd_rn(r[1], __fmul_rn(depth, r[4]));
+    g.oz = __fadd_rn(r[2], __fmul_rn(depth, r[5]));
+    g.dx = -r[8]; g.dy = -r[9]; g.dz = -r[10];
+    g.near = 0.f;
+    return g;
+}
+EO_DEV RayGeom ray_geom(const SampleArgs& a, int ray) {
+    const float* r = a.rays + (size_t)ray * 11;
+    RayGeom g;
+    if (a.sun_pass) {
+        g = sun_geom(r, a.depth[(size_t)ray * a.depth_stride]);
+    } else {
+        g.ox = r[0]; g.oy = r[1]; g.oz = r[2]; g.dx = r[3]; g.dy = r[4]; g.dz = r[5];
+        g.near = r[6];
+    }
+    return g;
+}
+
 // ---- ambient head for one ray, computed by the whole wave (radiance_fields/eonerf.py:132-139,163-164) ------
 struct AmbientRay { float out[3]; float hid[2]; float pre[3]; float enc[27]; };
 

@@ -148,13 +148,14 @@ def dsm_mae(gt, sec, transform, water=None, return_err=False):
 
 
 def evaluate_dsm(field, gt, roi, scene_offset, scene_scale, sun, chunk=5120, render_step_size=None, water=None, scaling=False,
-                 h=None, w=None, noise=None, return_all=False, occupancy_grid=None):
+                 h=None, w=None, noise=None, return_all=False, occupancy_grid=None, early_stop_eps=0.0, march_block=32):
     """Validation DSM MAE of a field against a lidar DSM, as train_eonerf.py:197-282 / eval_eonerf.py:286-324 obtain it:
     nadir rays (h x w, default the GT's size) -> render_image(only_depth=True) in the field's export precision -> raster on the GT's
     grid (roi = x, y, size, res) -> water mask -> registration -> MAE.
     sun = (elevation_deg, azimuth_deg) as create_rays_from_nadir receives them.  Returns device tensors: double[2] = MAE, n_valid
     (return_all: a dict with the rays, depth, dsm, transform and error raster as well).  Nothing here reads a result back: the only
-    host synchronisation is render_image's own sample count, and the caller's read of the MAE."""
+    host synchronisation is render_image's own sample count, and the caller's read of the MAE.
+    occupancy_grid, early_stop_eps, march_block: handed to render_image."""
     from .datasets.satellite import define_satrays_from_tensors
     from .sat_rendering import render_image
     gt = _raster(gt)
@@ -168,7 +169,8 @@ def evaluate_dsm(field, gt, roi, scene_offset, scene_scale, sun, chunk=5120, ren
             render_step_size = math.nextafter(render_step_size, 0.0)
     with torch.no_grad():
         res, _ = render_image(field, occupancy_grid, define_satrays_from_tensors(rays, ts), None, None, epoch_idx=None, chunk=chunk,
-                              render_step_size=render_step_size, only_depth=True, eval=True, noise=noise)
+                              render_step_size=render_step_size, only_depth=True, eval=True, noise=noise,
+                              early_stop_eps=early_stop_eps, march_block=march_block)
     depth = res["depth"].reshape(-1)
     dsm = rasterize_dsm(rays, depth, scene_offset, scene_scale, roi=roi)
     if water is not None:

@@ -132,9 +132,30 @@ class _RenderChunk(torch.autograd.Function):
         return (None,) * 9 + tuple(field.grad_views(d_flat))
 
 
-def render_rays_chunk(radiance_field, table, img, epoch_idx, eval=False, only_depth=False, noise=None, occupancy_grid=None):
+def _march_chunk(field, table, img, flags, u_cam, u_retry, u_sun, grid, early_stop_eps, march_block):
+    """One EXPORT chunk through eonerf_render_forward_march (include/eonerf_march.h): the chunk in rounds of march_block sampler slots,
+    rays below early_stop_eps of transmittance leave.  Same context choice, grid handling and outputs as an export chunk of _RenderChunk."""
+    L = _lib.lib()
+    native, flat = field._native(True)
+    n, dev = table.shape[0], table.device
+    nb = L.eonerf_march_workspace_bytes(native, n, flags, march_block)
+    if n and not nb:
+        raise ValueError(f"march_block={march_block}: the march runs in rounds of 16, 32 or 64 sampler slots")
+    ws = field._workspace("march", nb)
+    out = torch.empty(n, 21, dtype=torch.float32, device=dev)
+    n_samples = torch.zeros(1, dtype=torch.int32, device=dev)
+    with grid_on(native, grid):
+        _lib.check(L.eonerf_render_forward_march(native, _ptr(flat), _ptr(table), _ptr(img), _ptr(_zsteps(dev, field._n_samples)),
+                                                 _ptr(u_cam), _ptr(u_retry), _ptr(u_sun), n, flags, C.c_float(early_stop_eps), march_block,
+                                                 _ptr(out), _ptr(n_samples), None, _ptr(ws), ws.numel(), _stream()))
+    return out, n_samples
+
+
+def render_rays_chunk(radiance_field, table, img, epoch_idx, eval=False, only_depth=False, noise=None, occupancy_grid=None,
+                      early_stop_eps=0.0, march_block=32):
     """table [n,11] fp32, img [n] int64 -> (out [n,21], n_samples int32[1]) for one chunk.  occupancy_grid: an OccupancyGrid an
-    EXPORT chunk culls by; a training chunk, a non-export chunk and any other object ignore it."""
+    EXPORT chunk culls by; a training chunk, a non-export chunk and any other object ignore it.  early_stop_eps > 0: an EXPORT chunk
+    (the same condition) marches in rounds of march_block slots and drops rays below that transmittance; every other chunk ignores it."""
     # an EXPORT render: eval=True (eval_eonerf.py:311-324) or a module in .eval() mode outside autograd (train_eonerf.py:197-226)
     export = bool(eval) or (not radiance_field.training and not torch.is_grad_enabled())
     n, dev = table.shape[0], table.device
@@ -153,6 +174,8 @@ def render_rays_chunk(radiance_field, table, img, epoch_idx, eval=False, only_de
     else:
         u_cam, u_retry, u_sun = (None if t is None else t.to(dev, torch.float32).contiguous() for t in noise)
     grid = occupancy_grid if (isinstance(occupancy_grid, OccupancyGrid) and export and not flags & _lib.F_TRAIN) else None
+    if early_stop_eps > 0 and export and not flags & _lib.F_TRAIN:
+        return _march_chunk(radiance_field, table, img, flags, u_cam, u_retry, u_sun, grid, float(early_stop_eps), int(march_block))
     return _RenderChunk.apply(radiance_field, table, img, flags, export, u_cam, u_retry, u_sun, grid, *params)
 
 
@@ -165,7 +188,7 @@ def render_image(
     args,
     epoch_idx=None,
     chunk: int = 5120,
-    # rendering options (accepted and ignored exactly as the reference's live sampler ignores them)
+    # rendering options (accepted and ignored exactly as the reference's live sampler ignores them -- but early_stop_eps, below)
     near_plane=None,
     far_plane=None,
     render_step_size: float = 1e-3,
@@ -177,11 +200,16 @@ def render_image(
     only_depth: bool = False,
     eval: bool = False,
     noise=None,
+    march_block: int = 32,
 ):
     """Render the pixels of an image (sat_rendering.py:176-335).  Returns (results dict, n_rendering_samples).
     occupancy_grid: an eonerf_code_amd.occupancy.OccupancyGrid makes an EXPORT render (eval=True, or a module in .eval() mode under
     no_grad) skip the samples of empty cells -- pts_per_ray / sc_pts_per_ray and n_rendering_samples then count the kept samples; a
-    training call, and None or any other object (the reference passes its never-sampled nerfacc estimator), ignore it."""
+    training call, and None or any other object (the reference passes its never-sampled nerfacc estimator), ignore it.
+    early_stop_eps > 0 makes an EXPORT render (the same condition) stop a ray once its transmittance has fallen below it, checked every
+    march_block (16, 32 or 64) sampler slots (include/eonerf_march.h): the camera columns move by at most 2 eps (depth) / eps against
+    eps = 0, pts_per_ray / sc_pts_per_ray stay the full counts and n_rendering_samples counts the kept camera samples.  With 0 (the
+    default), in training and in every non-export call the existing entry point runs."""
     radiance_field._context()
     radiance_field.set_n_samples(n_samples_of(render_step_size))
     if isinstance(occupancy_grid, OccupancyGrid):
@@ -201,7 +229,8 @@ def render_image(
         for k, i in enumerate(range(0, num_rays, chunk)):
             nz = None if noise is None else noise[k]
             out, n = render_rays_chunk(radiance_field, table[i:i + chunk], img[i:i + chunk], epoch_idx, eval=eval,
-                                       only_depth=only_depth, noise=nz, occupancy_grid=occupancy_grid)
+                                       only_depth=only_depth, noise=nz, occupancy_grid=occupancy_grid,
+                                       early_stop_eps=early_stop_eps, march_block=march_block)
             outs.append(out)
             counts.append(n)
         out = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]

@@ -55,7 +55,8 @@ def _step_size_of(field):
     return math.nextafter(step, 0.0) if int(2 / step) < field._n_samples else step
 
 
-def validate_images(field, images, epoch_idx, chunk=5120, render_step_size=None, gt=None, max_images=5, noise=None, occupancy_grid=None):
+def validate_images(field, images, epoch_idx, chunk=5120, render_step_size=None, gt=None, max_images=5, noise=None, occupancy_grid=None,
+                    early_stop_eps=0.0, march_block=32):
     """The validation loop of train_eonerf.py:197-294 over images = [{"rays": [h*w, 11], "rgbs": [h*w, 3], "h", "w"}, ...], the first
     min(max_images, len(images)) of them (:200).  Per image: render_image under no_grad with the module in .eval() mode -- i.e. in
     the field's export precision -- with epoch_idx and chunk as given, then image_metrics on results["rgb"] / results["beta"].
@@ -76,7 +77,8 @@ def validate_images(field, images, epoch_idx, chunk=5120, render_step_size=None,
     :259), so without one it logs no val/loss or val/psnr at all; here the image metrics are reported without a ground truth too.
 
     noise: None (production: the sampler kernels draw the jitter) or one render_image `noise` argument per image (parity tests).
-    occupancy_grid: handed to render_image (an OccupancyGrid: the renders skip the samples of empty cells)."""
+    occupancy_grid: handed to render_image (an OccupancyGrid: the renders skip the samples of empty cells).
+    early_stop_eps, march_block: handed to render_image (> 0: the renders stop rays below that transmittance)."""
     from .datasets.satellite import define_satrays_from_tensors
     from .sat_rendering import render_image
     images = list(images)[:max(0, int(max_images))]
@@ -102,7 +104,8 @@ def validate_images(field, images, epoch_idx, chunk=5120, render_step_size=None,
                     raise ValueError(f"validate_images: image {i} needs rays [h*w, 11] and rgbs [h*w, 3]")
                 ts = torch.zeros(rays.shape[0], 1, dtype=torch.int64, device=dev)           # :207 -- image index 0 for every image
                 results, _ = render_image(field, occupancy_grid, define_satrays_from_tensors(rays, ts), None, None, epoch_idx=epoch_idx, chunk=chunk,
-                                          render_step_size=render_step_size, noise=None if noise is None else noise[i])
+                                          render_step_size=render_step_size, noise=None if noise is None else noise[i],
+                                          early_stop_eps=early_stop_eps, march_block=march_block)
                 m = image_metrics(results["rgb"], pixels, results["beta"])                  # :229-230
                 table[i, 0:5] = m[0:5]
                 table[i, 6] = m[5]
