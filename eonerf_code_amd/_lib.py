@@ -40,6 +40,8 @@ OCC_SYMBOLS = ["eonerf_occ_version", "eonerf_occ_workspace_bytes", "eonerf_occ_u
                "eonerf_occ_sample_rays"]
 # include/eonerf_march.h: block-wise early ray termination of export renders (sat_rendering.render_image(early_stop_eps=...))
 MARCH_SYMBOLS = ["eonerf_march_version", "eonerf_march_workspace_bytes", "eonerf_render_forward_march", "eonerf_march_sample_round"]
+# include/eonerf_quantile.h: quantile depth of export renders (sat_rendering.render_depth_quantiles)
+QUANTILE_SYMBOLS = ["eonerf_quantile_version", "eonerf_quantile_workspace_bytes", "eonerf_render_depth_quantiles"]
 
 
 class EonerfRpc(C.Structure):
@@ -66,6 +68,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_sweep.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_occ.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_march.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_quantile.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -195,7 +198,11 @@ def lib():
     L.eonerf_march_workspace_bytes.argtypes = [vp, i, i, i]
     L.eonerf_render_forward_march.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, fp, i, vp, vp, vp, vp, sz, vp]
     L.eonerf_march_sample_round.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, sz, vp]
-    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS:
+    L.eonerf_quantile_version.restype = i
+    L.eonerf_quantile_workspace_bytes.restype = sz
+    L.eonerf_quantile_workspace_bytes.argtypes = [vp, i, i, i]
+    L.eonerf_render_depth_quantiles.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, fp, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS + QUANTILE_SYMBOLS:
         getattr(L, name)
     _lib = L
     return L

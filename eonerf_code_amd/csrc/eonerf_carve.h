@@ -198,6 +198,30 @@ inline int march_refusal(int flags, float early_stop_eps, int block, size_t ws_b
     return EONERF_OK;
 }
 
+// ---- eonerf_render_depth_quantiles (include/eonerf_quantile.h): the layout of the pass it runs -- dense (block == 0): carve_render's
+//      ONLY_DEPTH layout unchanged, so that the sampler and chain launches see the forward's; march: carve_march's -- followed by the
+//      sampler's flattened outputs (ray index, interval ends) of that pass' sample capacity ----
+constexpr int QUANTILE_MAX = 8;
+inline bool quantile_block_ok(int block) { return block == 0 || march_block_ok(block); }
+struct QuantileWs { RenderWs r; MarchWs m; int64_t* o_ray; float *o_ts, *o_te; int p_cap; size_t bytes; };
+inline QuantileWs carve_quantile(const CarveCfg& cfg, void* base, int n_rays, int block) {
+    QuantileWs q;
+    memset(&q, 0, sizeof(q));
+    Carver c(base);
+    if (block == 0) {
+        q.r = carve_render(cfg, base, n_rays, EONERF_F_ONLY_DEPTH);
+        q.p_cap = p_cap_of(n_rays, cfg.n_samples);
+        c.off = q.r.bytes - 256;      // (where the pass' own allocator stopped)
+    } else {
+        q.m = carve_march(cfg, base, n_rays, EONERF_F_ONLY_DEPTH, block);
+        q.p_cap = q.m.p_cap;
+        c.off = q.m.bytes - 256;
+    }
+    q.o_ray = c.take<int64_t>(q.p_cap); q.o_ts = c.take<float>(q.p_cap); q.o_te = c.take<float>(q.p_cap);
+    q.bytes = c.off + 256;
+    return q;
+}
+
 // Everything a pipelined backward call needs zeroed, as ONE span: [bottleneck factors | GEMM work queue | the PIPE_LAUNCHES sync blocks].
 // Cleared by the call's first kernel (ShadeBwdArgs::zero_base) or by the memset in front of its first pipelined launch
 struct ZeroSpan { uint8_t* base; size_t bytes; };

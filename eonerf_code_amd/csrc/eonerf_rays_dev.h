@@ -230,7 +230,7 @@ EO_DEV AmbientRay ambient_forward(const AmbientW& w, float sx, float sy, float s
 //   call sites radiance_fields/eonerf.py:229-243)            per-ray sums of w*{mid, albedo, ts, tb, 1}
 // SPL = samples per lane: a ray has n_samples - 1 = 64 SPL - 1 intervals at most (n_samples = int(2 / render_step_size) = 64, 128 or
 // 256, sat_rendering.py:64), element i = lane + 64 k sits in slot k of its lane
-template <int SPL> struct RayWeights { float w[SPL], T[SPL], sd[SPL]; float total; };
+template <int SPL> struct RayWeights { float w[SPL], T[SPL], sd[SPL]; float total; float ex[SPL]; };      // ex: the exclusive prefix of sd (T = exp(-ex))
 
 template <int SPL>
 EO_DEV RayWeights<SPL> ray_weights(const float* sigma, const float* delta, int off, int n, int lane) {
@@ -242,19 +242,19 @@ EO_DEV RayWeights<SPL> ray_weights(const float* sigma, const float* delta, int o
     }
     // exclusive prefix = inclusive prefix of the PREVIOUS lane (never "inclusive - self": the last interval has
     // sigma*delta ~ 1e10 and would cancel the whole prefix), plus the total of the 64-element groups in front
-    float carry = 0.f, ex[SPL];
+    float carry = 0.f;
 #pragma unroll
     for (int k = 0; k < SPL; ++k) {
         const float inc = wave_incl_scan(r.sd[k], lane);
         const float prev = __shfl_up(inc, 1, 64);
-        ex[k] = lane == 0 ? carry : carry + prev;
+        r.ex[k] = lane == 0 ? carry : carry + prev;
         carry += __shfl(inc, 63, 64);
     }
     r.total = carry;
 #pragma unroll
     for (int k = 0; k < SPL; ++k) {
         const int i = lane + 64 * k;
-        r.T[k] = expf(-ex[k]);
+        r.T[k] = expf(-r.ex[k]);
         r.w[k] = i < n ? r.T[k] * (1.f - expf(-r.sd[k])) : 0.f;
     }
     return r;

@@ -148,16 +148,19 @@ def dsm_mae(gt, sec, transform, water=None, return_err=False):
 
 
 def evaluate_dsm(field, gt, roi, scene_offset, scene_scale, sun, chunk=5120, render_step_size=None, water=None, scaling=False,
-                 h=None, w=None, noise=None, return_all=False, occupancy_grid=None, early_stop_eps=0.0, march_block=32):
+                 h=None, w=None, noise=None, return_all=False, occupancy_grid=None, early_stop_eps=0.0, march_block=32, depth_quantile=None):
     """Validation DSM MAE of a field against a lidar DSM, as train_eonerf.py:197-282 / eval_eonerf.py:286-324 obtain it:
     nadir rays (h x w, default the GT's size) -> render_image(only_depth=True) in the field's export precision -> raster on the GT's
     grid (roi = x, y, size, res) -> water mask -> registration -> MAE.
     sun = (elevation_deg, azimuth_deg) as create_rays_from_nadir receives them.  Returns device tensors: double[2] = MAE, n_valid
     (return_all: a dict with the rays, depth, dsm, transform and error raster as well).  Nothing here reads a result back: the only
     host synchronisation is render_image's own sample count, and the caller's read of the MAE.
-    occupancy_grid, early_stop_eps, march_block: handed to render_image."""
+    occupancy_grid, early_stop_eps, march_block: handed to render_image.
+    depth_quantile: None, or a quantile q in (0, 1): the raster is made from the depth at which the rays' accumulated opacity crosses q
+    (0.5: the median surface; sat_rendering.render_depth_quantiles, include/eonerf_quantile.h) instead of the expected depth; with
+    return_all the dict then also carries "depth_expected" and "od_front"."""
     from .datasets.satellite import define_satrays_from_tensors
-    from .sat_rendering import render_image
+    from .sat_rendering import render_depth_quantiles, render_image
     gt = _raster(gt)
     h, w = int(h or gt.shape[0]), int(w or gt.shape[1])
     rays = nadir_rays(h, w, scene_scale, sun[0], sun[1], device=gt.device)
@@ -167,11 +170,16 @@ def evaluate_dsm(field, gt, roi, scene_offset, scene_scale, sun, chunk=5120, ren
         render_step_size = 2.0 / field._n_samples
         if int(2 / render_step_size) < field._n_samples:
             render_step_size = math.nextafter(render_step_size, 0.0)
-    with torch.no_grad():
-        res, _ = render_image(field, occupancy_grid, define_satrays_from_tensors(rays, ts), None, None, epoch_idx=None, chunk=chunk,
-                              render_step_size=render_step_size, only_depth=True, eval=True, noise=noise,
-                              early_stop_eps=early_stop_eps, march_block=march_block)
-    depth = res["depth"].reshape(-1)
+    if depth_quantile is not None:
+        res, _ = render_depth_quantiles(field, occupancy_grid, define_satrays_from_tensors(rays, ts), quantiles=(depth_quantile,), chunk=chunk,
+                                        render_step_size=render_step_size, noise=noise, early_stop_eps=early_stop_eps, march_block=march_block)
+        depth = res["depth_q"].reshape(-1)
+    else:
+        with torch.no_grad():
+            res, _ = render_image(field, occupancy_grid, define_satrays_from_tensors(rays, ts), None, None, epoch_idx=None, chunk=chunk,
+                                  render_step_size=render_step_size, only_depth=True, eval=True, noise=noise,
+                                  early_stop_eps=early_stop_eps, march_block=march_block)
+        depth = res["depth"].reshape(-1)
     dsm = rasterize_dsm(rays, depth, scene_offset, scene_scale, roi=roi)
     if water is not None:
         dsm = mask_water(dsm, water)
@@ -179,4 +187,7 @@ def evaluate_dsm(field, gt, roi, scene_offset, scene_scale, sun, chunk=5120, ren
     out = dsm_mae(gt, dsm, transform, return_err=return_all)
     if not return_all:
         return out
-    return {"mae": out[0], "err": out[1], "rays": rays, "depth": depth, "dsm": dsm, "transform": transform}
+    all_ = {"mae": out[0], "err": out[1], "rays": rays, "depth": depth, "dsm": dsm, "transform": transform}
+    if depth_quantile is not None:
+        all_["depth_expected"], all_["od_front"] = res["depth"].reshape(-1), res["od_front"].reshape(-1)
+    return all_

@@ -248,3 +248,96 @@ def render_image(
         return {"depth": out[:, 3:4].reshape(*lead, -1)}, n_rendering_samples
     results = {k: out[:, a:b].reshape(*lead, -1) for k, a, b in RESULT_SLICES}
     return results, n_rendering_samples
+
+
+QUANTILE_MAX = 8
+
+
+def check_quantile_args(quantiles, early_stop_eps=0.0, march_block=32):
+    """The argument rules of eonerf_render_depth_quantiles (include/eonerf_quantile.h), on the host and without the library: 1 .. 8
+    strictly increasing quantiles in (0, 1) as fp32; early_stop_eps in [0, 1); with early_stop_eps > 0 a block of 16, 32 or 64 and
+    L_qmax * (1 + 1e-4) < -log(eps), so that every bracket lies among the samples the march keeps.
+    Returns (the quantiles as a tuple of the fp32 values the library will see, eps as float).  ValueError otherwise."""
+    import math
+    try:
+        qs = [float(q) for q in quantiles]
+    except TypeError:
+        qs = [float(quantiles)]
+    qs = tuple(C.c_float(q).value for q in qs)      # what the fp32 array holds
+    if not 1 <= len(qs) <= QUANTILE_MAX:
+        raise ValueError(f"{len(qs)} quantiles: a call takes 1 .. {QUANTILE_MAX}")
+    for j, q in enumerate(qs):
+        if not 0.0 < q < 1.0:      # (NaN fails both comparisons)
+            raise ValueError(f"quantile {q!r} is not inside (0, 1)")
+        if j and not q > qs[j - 1]:
+            raise ValueError(f"quantiles must be strictly increasing: {qs[j - 1]!r} is followed by {q!r}")
+    eps = C.c_float(float(early_stop_eps)).value
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"early_stop_eps={early_stop_eps!r} is not inside [0, 1)")
+    if eps > 0.0:
+        if march_block not in (16, 32, 64):
+            raise ValueError(f"march_block={march_block}: the march runs in rounds of 16, 32 or 64 sampler slots")
+        l_max = -math.log1p(-qs[-1])
+        if not l_max * (1.0 + 1e-4) < -math.log(eps):
+            raise ValueError(f"quantile {qs[-1]!r} lies behind the point where early_stop_eps={eps!r} ends a ray "
+                             f"(needs q < 1 - eps: -log1p(-q) * (1 + 1e-4) < -log(eps))")
+    return qs, eps
+
+
+@torch.no_grad()
+def render_depth_quantiles(radiance_field, occupancy_grid, rays: SatRays, quantiles=(0.5,), chunk: int = 5120,
+                           render_step_size: float = 1e-3, noise=None, early_stop_eps: float = 0.0, march_block: int = 32):
+    """Quantile depth of an EXPORT render (include/eonerf_quantile.h): per ray the distance at which its accumulated opacity crosses each
+    of `quantiles` (0.5: the median surface; a 0.16 / 0.84 pair: a confidence band), beside the expected depth render_image(only_depth=True)
+    gives.  Returns ({"depth": [..., 1] the expected depth, "od_front": [..., 1] the optical depth in front of the ray's last sample,
+    "depth_q": [..., len(quantiles)]}, n_rendering_samples).
+    Always under no_grad, on the field's export context, with the fp16x3 range retry, the chunk loop and the single host synchronisation
+    of render_image.  occupancy_grid: an OccupancyGrid culls as in an export render_image; early_stop_eps > 0 marches in rounds of
+    march_block slots (the quantiles do not move beyond the order of the fp32 sums; "depth" carries the march's 2 eps bound).
+    noise: per chunk (u_cam, u_retry[, ...]) as render_image's."""
+    qs, eps = check_quantile_args(quantiles, early_stop_eps, march_block)
+    n_q = len(qs)
+    q_arr = (C.c_float * n_q)(*qs)
+    radiance_field._context()
+    radiance_field.set_n_samples(n_samples_of(render_step_size))
+    grid = occupancy_grid if isinstance(occupancy_grid, OccupancyGrid) else None
+    if grid is not None:
+        grid.check_step_size(render_step_size)
+    rays_shape = rays.origins.shape
+    if len(rays_shape) == 3:
+        height, width, _ = rays_shape
+        num_rays = height * width
+        rays = namedtuple_map(lambda r: r.reshape([num_rays] + list(r.shape[2:])), rays)
+    else:
+        num_rays, _ = rays_shape
+    table, _ = satrays_to_table(rays)
+    dev = table.device
+    L = _lib.lib()
+    block = int(march_block) if eps > 0 else 0
+    for _attempt in range(2):
+        native, flat = radiance_field._native(True)
+        zs = _zsteps(dev, radiance_field._n_samples)
+        outs, counts = [], []
+        for k, i in enumerate(range(0, num_rays, chunk)):
+            t = table[i:i + chunk]
+            n = t.shape[0]
+            u_cam = u_retry = None
+            if noise is not None:
+                u_cam, u_retry = (None if u is None else u.to(dev, torch.float32).contiguous() for u in noise[k][:2])
+            nb = L.eonerf_quantile_workspace_bytes(native, n, n_q, block)
+            ws = radiance_field._workspace("quantile", nb)
+            out = torch.empty(n, 2 + n_q, dtype=torch.float32, device=dev)
+            n_samples = torch.zeros(1, dtype=torch.int32, device=dev)
+            with grid_on(native, grid):
+                _lib.check(L.eonerf_render_depth_quantiles(native, _ptr(flat), _ptr(t), _ptr(zs), _ptr(u_cam), _ptr(u_retry), n, q_arr, n_q,
+                                                           C.c_float(eps), block, _ptr(out), _ptr(n_samples), None, None, None, None,
+                                                           _ptr(ws), ws.numel(), _stream()))
+            outs.append(out)
+            counts.append(n_samples)
+        out = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
+        n_rendering_samples = int(torch.stack(counts).sum().item())     # the only host sync of the call
+        if radiance_field._export_range_ok():      # (fp16x3 export context: render_image's retry on its fp32 context)
+            break
+    lead = tuple(rays_shape[:-1])
+    res = {"depth": out[:, 0:1].reshape(*lead, -1), "od_front": out[:, 1:2].reshape(*lead, -1), "depth_q": out[:, 2:].reshape(*lead, -1)}
+    return res, n_rendering_samples

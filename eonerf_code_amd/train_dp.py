@@ -71,6 +71,7 @@ def main():
     ap.add_argument("--occ_every", type=int, default=50, help="steps between occupancy grid updates (train_eonerf.py:112-119)")
     ap.add_argument("--early_stop_eps", type=float, default=0.0, help="validation renders stop a ray below this transmittance (0: off)")
     ap.add_argument("--march_block", type=int, default=32, help="sampler slots per round of a render with --early_stop_eps: 16, 32 or 64")
+    ap.add_argument("--dsm_quantile", type=float, default=None, help="val/mae and val/img_mae read the depth at this opacity quantile (0.5: the median surface) instead of the expected depth")
     args = ap.parse_args()
 
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -191,7 +192,7 @@ def main():
                 sun = [float(x) for x in gt.get("sun", (0.0, 0.0))]
                 mae = evaluate_dsm(field, gt["dsm"], [float(x) for x in gt["roi"]], gt["scene_offset"], gt["scene_scale"], sun,
                                    chunk=args.val_chunk, water=gt["water"], occupancy_grid=occ,
-                                   early_stop_eps=args.early_stop_eps, march_block=args.march_block)
+                                   early_stop_eps=args.early_stop_eps, march_block=args.march_block, depth_quantile=args.dsm_quantile)
                 mae, n_valid = mae.tolist()                                 # the validation's one read-back
                 print(f"epoch={epoch} | elapsed_time={time.time() - tic:.2f}s | step={step} | val/mae={mae:.4f} | val/cells={int(n_valid)}", flush=True)
         if args.val_images:                                                 # the held-out images of the same block (:199-294)
@@ -200,7 +201,7 @@ def main():
             if rank == 0 and val_images:
                 from .validation import validate_images
                 _, means = validate_images(field, val_images, epoch, chunk=args.val_chunk, gt=gt, max_images=args.val_max, occupancy_grid=occ,
-                                           early_stop_eps=args.early_stop_eps, march_block=args.march_block)
+                                           early_stop_eps=args.early_stop_eps, march_block=args.march_block, depth_quantile=args.dsm_quantile)
                 names = ("loss", "coarse_color", "coarse_logbeta", "psnr") + (("mae",) if gt is not None else ())
                 vals = torch.stack([means[k] for k in names]).tolist()      # the validation's one read-back
                 line = (f"epoch={epoch} | elapsed_time={time.time() - tic:.2f}s | step={step} | val/loss={vals[0]:.5f} | "

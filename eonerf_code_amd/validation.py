@@ -56,7 +56,7 @@ def _step_size_of(field):
 
 
 def validate_images(field, images, epoch_idx, chunk=5120, render_step_size=None, gt=None, max_images=5, noise=None, occupancy_grid=None,
-                    early_stop_eps=0.0, march_block=32):
+                    early_stop_eps=0.0, march_block=32, depth_quantile=None):
     """The validation loop of train_eonerf.py:197-294 over images = [{"rays": [h*w, 11], "rgbs": [h*w, 3], "h", "w"}, ...], the first
     min(max_images, len(images)) of them (:200).  Per image: render_image under no_grad with the module in .eval() mode -- i.e. in
     the field's export precision -- with epoch_idx and chunk as given, then image_metrics on results["rgb"] / results["beta"].
@@ -78,9 +78,11 @@ def validate_images(field, images, epoch_idx, chunk=5120, render_step_size=None,
 
     noise: None (production: the sampler kernels draw the jitter) or one render_image `noise` argument per image (parity tests).
     occupancy_grid: handed to render_image (an OccupancyGrid: the renders skip the samples of empty cells).
-    early_stop_eps, march_block: handed to render_image (> 0: the renders stop rays below that transmittance)."""
+    early_stop_eps, march_block: handed to render_image (> 0: the renders stop rays below that transmittance).
+    depth_quantile: None, or a quantile q in (0, 1): with gt, the image's DSM is made from the depth at which its rays' accumulated
+    opacity crosses q (one sat_rendering.render_depth_quantiles pass over the image's rays) instead of the rendered expected depth."""
     from .datasets.satellite import define_satrays_from_tensors
-    from .sat_rendering import render_image
+    from .sat_rendering import render_depth_quantiles, render_image
     images = list(images)[:max(0, int(max_images))]
     if not images:
         raise ValueError("validate_images: no images")
@@ -103,14 +105,20 @@ def validate_images(field, images, epoch_idx, chunk=5120, render_step_size=None,
                 if rays.dim() != 2 or rays.shape[1] != 11 or rays.shape[0] != int(data["h"]) * int(data["w"]) or pixels.shape[0] != rays.shape[0]:
                     raise ValueError(f"validate_images: image {i} needs rays [h*w, 11] and rgbs [h*w, 3]")
                 ts = torch.zeros(rays.shape[0], 1, dtype=torch.int64, device=dev)           # :207 -- image index 0 for every image
-                results, _ = render_image(field, occupancy_grid, define_satrays_from_tensors(rays, ts), None, None, epoch_idx=epoch_idx, chunk=chunk,
+                sat = define_satrays_from_tensors(rays, ts)
+                results, _ = render_image(field, occupancy_grid, sat, None, None, epoch_idx=epoch_idx, chunk=chunk,
                                           render_step_size=render_step_size, noise=None if noise is None else noise[i],
                                           early_stop_eps=early_stop_eps, march_block=march_block)
                 m = image_metrics(results["rgb"], pixels, results["beta"])                  # :229-230
                 table[i, 0:5] = m[0:5]
                 table[i, 6] = m[5]
                 if gt is not None:                                                          # :259-289
-                    dsm = rasterize_dsm(rays, results["depth"].reshape(-1), gt["scene_offset"], gt["scene_scale"], roi=roi)
+                    depth = results["depth"]
+                    if depth_quantile is not None:
+                        depth = render_depth_quantiles(field, occupancy_grid, sat, quantiles=(depth_quantile,), chunk=chunk,
+                                                       render_step_size=render_step_size, noise=None if noise is None else noise[i],
+                                                       early_stop_eps=early_stop_eps, march_block=march_block)[0]["depth_q"]
+                    dsm = rasterize_dsm(rays, depth.reshape(-1), gt["scene_offset"], gt["scene_scale"], roi=roi)
                     if water is not None:
                         dsm = mask_water(dsm, water)
                     table[i, 5] = dsm_mae(gt_dsm, dsm, register_dsm(gt_dsm, dsm, scaling=False))[0]
