@@ -42,6 +42,8 @@ OCC_SYMBOLS = ["eonerf_occ_version", "eonerf_occ_workspace_bytes", "eonerf_occ_u
 MARCH_SYMBOLS = ["eonerf_march_version", "eonerf_march_workspace_bytes", "eonerf_render_forward_march", "eonerf_march_sample_round"]
 # include/eonerf_quantile.h: quantile depth of export renders (sat_rendering.render_depth_quantiles)
 QUANTILE_SYMBOLS = ["eonerf_quantile_version", "eonerf_quantile_workspace_bytes", "eonerf_render_depth_quantiles"]
+# include/eonerf_ortho.h: the stateless true-orthophoto group (ortho.py): surface points, per-image gather, fusion
+ORTHO_SYMBOLS = ["eonerf_ortho_version", "eonerf_ortho_ground", "eonerf_ortho_gather", "eonerf_ortho_fuse"]
 
 
 class EonerfRpc(C.Structure):
@@ -69,6 +71,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_occ.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_march.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_quantile.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_ortho.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -202,7 +205,13 @@ def lib():
     L.eonerf_quantile_workspace_bytes.restype = sz
     L.eonerf_quantile_workspace_bytes.argtypes = [vp, i, i, i]
     L.eonerf_render_depth_quantiles.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, fp, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    for name in SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS + QUANTILE_SYMBOLS:
+    L.eonerf_ortho_version.restype = i
+    f3 = C.POINTER(fp)
+    L.eonerf_ortho_ground.argtypes = [vp, i, vp, C.c_long, f3, f3, i, i, vp, vp]
+    L.eonerf_ortho_gather.argtypes = [vp, C.c_long, C.POINTER(EonerfRpc), vp, i, i, i, f3, f3, vp, fp, vp, vp, vp, vp]
+    L.eonerf_ortho_fuse.argtypes = [vp, vp, i, C.c_long, i, i, vp, vp, vp, vp]
+    for name in (SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS + QUANTILE_SYMBOLS
+                 + ORTHO_SYMBOLS):
         getattr(L, name)
     _lib = L
     return L

@@ -3,6 +3,7 @@
 // Follows sat_utils.py:310-362,420-432 and datasets/satellite.py:644-653,677-679 of the reference.  pyproj's Transformer belongs to an
 // un-vendored package and is restated from its published algorithm:
 //   PROJ "+proj=utm" (etmerc), inverse   (6th-order Krueger series, beta coefficients; Newton on tan(lat) from the conformal latitude)
+// -- utm_inverse of eonerf_rpc_dev.h, shared with eonerf_ortho.hip.
 // Everything is fp64 (one thread per sample point / per pixel) until the one cast to fp32 of each output.
 // Built with -ffp-contract=off: the reference's numpy / torch arithmetic is unfused.
 // Reproducibility: numpy's fancy-index assignment keeps, for a pixel hit several times, the LAST point in raveled order.  "Last" is the
@@ -21,7 +22,6 @@
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kNewton = 5;          // iterations on tan(lat): quadratic convergence from a 0.7 % start, round-off after three
 
 struct PriorArgs {
     RpcModel rpc; UtmParams utm;
@@ -48,31 +48,6 @@ __device__ __forceinline__ size_t source_cell(const PriorArgs& a, uint32_t p) {
     const int i = (int)(p / (uint32_t)(2 * a.w)), j = (int)(p % (uint32_t)(2 * a.w));
     const int r = (int)linspace_at(0.0, (double)(a.h - 1), 2 * a.h, i), c = (int)linspace_at(0.0, (double)(a.w - 1), 2 * a.w, j);
     return (size_t)r * a.w + c;
-}
-
-// WGS84 transverse Mercator, inverse 6th-order Krueger series (PROJ etmerc; Karney 2011 eqs. 11, 36 and 19-21)
-__device__ void utm_inverse(const UtmParams& u, const double* beta, double east, double north, double& lon_deg, double& lat_deg) {
-    const double r2d = 57.29577951308232;
-    const double xi = (north - u.false_north) / u.k0A, eta = (east - 500000.0) / u.k0A;
-    double xi_p = xi, eta_p = eta;
-#pragma unroll
-    for (int j = 1; j <= 6; ++j) {
-        xi_p -= beta[j - 1] * sin(2 * j * xi) * cosh(2 * j * eta);
-        eta_p -= beta[j - 1] * cos(2 * j * xi) * sinh(2 * j * eta);
-    }
-    const double sh = sinh(eta_p), c = cos(xi_p);
-    const double lam = atan2(sh, c);
-    const double taup = sin(xi_p) / sqrt(sh * sh + c * c);          // tan of the conformal latitude
-    const double e2m = 1.0 - u.e * u.e;
-    double tau = taup / e2m;
-    for (int k = 0; k < kNewton; ++k) {
-        const double tau1 = sqrt(1.0 + tau * tau);
-        const double sig = sinh(u.e * atanh(u.e * tau / tau1));
-        const double taupa = sqrt(1.0 + sig * sig) * tau - sig * tau1;
-        tau += (taup - taupa) * (1.0 + e2m * tau * tau) / (e2m * tau1 * sqrt(1.0 + taupa * taupa));
-    }
-    lat_deg = atan(tau) * r2d;
-    lon_deg = u.lon0_deg + lam * r2d;
 }
 
 __global__ __launch_bounds__(kBlock) void k_prior_splat(PriorArgs a) {
@@ -143,15 +118,7 @@ int eonerf_prior_reproject(const float* dsm, const float* values, int h, int w, 
     PriorArgs a;
     memcpy(&a.rpc, rpc, sizeof(RpcModel));
     a.utm = eo_utm_params(utm_zone, south);
-    // Krueger series, inverse direction (Karney 2011, eq. 36)
-    const double f = 1.0 / 298.257223563, nn = f / (2.0 - f);
-    const double n2 = nn * nn, n3 = n2 * nn, n4 = n3 * nn, n5 = n4 * nn, n6 = n5 * nn;
-    a.beta[0] = nn / 2 - 2 * n2 / 3 + 37 * n3 / 96 - n4 / 360 - 81 * n5 / 512 + 96199 * n6 / 604800;
-    a.beta[1] = n2 / 48 + n3 / 15 - 437 * n4 / 1440 + 46 * n5 / 105 - 1118711 * n6 / 3870720;
-    a.beta[2] = 17 * n3 / 480 - 37 * n4 / 840 - 209 * n5 / 4480 + 5569 * n6 / 90720;
-    a.beta[3] = 4397 * n4 / 161280 - 11 * n5 / 504 - 830251 * n6 / 7257600;
-    a.beta[4] = 4583 * n5 / 161280 - 108847 * n6 / 3991680;
-    a.beta[5] = 20648693 * n6 / 638668800;
+    eo_krueger_beta(a.beta);
     a.dsm = dsm; a.values = values ? values : dsm;
     a.h = h; a.w = w; a.out_h = out_h; a.out_w = out_w;
     a.x_min = fmin(bounds[0], bounds[2]); a.x_max = fmax(bounds[0], bounds[2]);     // sat_utils.py:318-321

@@ -26,6 +26,12 @@ over its own rays.  Without it nothing changes.
 every `--occ_every` steps on the training context (eonerf_code_amd.occupancy.OccupancyGrid), the per-epoch validation renders
 (`--gt_dsm`, `--val_images`) skip the samples of its empty cells (the grid dilated by one cell), and checkpoints carry it.  The training
 step itself never reads the grid.  Without the flag nothing changes.
+
+`--ortho` is a torch file {"images": K tensors [h_k, w_k, C], "rpcs": one rpcm dict per image, "size": [h, w] of the mosaic, "min_alt",
+"max_alt", "scene_offset": [3], "scene_scale": [3], "zone", "south"}.  With it, after the last step, rank 0 makes the true orthophoto
+of the images on the nadir grid (eonerf_code_amd.ortho.orthorectify: the images gathered through their RPCs on the rendered surface,
+occluded cells left out, median-fused) and torch.saves the result dict plus "geotransform" to `--ortho_out`.  `--occ_grid` and the step
+size reach that render as they reach the validation renders.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -72,6 +78,8 @@ def main():
     ap.add_argument("--early_stop_eps", type=float, default=0.0, help="validation renders stop a ray below this transmittance (0: off)")
     ap.add_argument("--march_block", type=int, default=32, help="sampler slots per round of a render with --early_stop_eps: 16, 32 or 64")
     ap.add_argument("--dsm_quantile", type=float, default=None, help="val/mae and val/img_mae read the depth at this opacity quantile (0.5: the median surface) instead of the expected depth")
+    ap.add_argument("--ortho", default=None, help="torch file with the input images, their RPCs, the mosaic size and the scene normalisation: true orthophoto after the last step")
+    ap.add_argument("--ortho_out", default=None, help="where rank 0 saves the orthophoto (default: <logs_dir>/<exp_name>/ortho.pt)")
     args = ap.parse_args()
 
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -145,6 +153,12 @@ def main():
         if rank == 0:
             val_images = [{"rays": im["rays"].to(dev, torch.float32), "rgbs": im["rgbs"].to(dev, torch.float32), "h": int(im["h"]),
                            "w": int(im["w"])} for im in v["images"][:max(0, args.val_max)]]
+    ortho = None
+    if args.ortho:
+        ortho = torch.load(args.ortho, map_location="cpu")
+        for key in ("images", "rpcs", "size", "min_alt", "max_alt", "scene_offset", "scene_scale", "zone", "south"):
+            if key not in ortho:
+                raise SystemExit(f"--ortho {args.ortho}: missing entry '{key}'")
     step, tic = 0, time.time()
     for epoch in range(10 ** 7):
         for i in range(steps_per_epoch):
@@ -179,6 +193,19 @@ def main():
                 save_checkpoint(os.path.join(args.logs_dir, args.exp_name, f"ckpts/epoch={epoch}.ckpt"), epoch, field, trainer, loss, occ_grid=occ)
             if step == args.max_train_steps:
                 trainer.check_device_status()
+                if ortho is not None and rank == 0:
+                    from .ortho import nadir_geotransform, orthorectify
+                    oh, ow = (int(x) for x in ortho["size"])
+                    k_img = len(ortho["images"])
+                    res = orthorectify(field, ortho["images"], ortho["rpcs"], ortho["scene_offset"], ortho["scene_scale"], int(ortho["zone"]),
+                                       bool(ortho["south"]), oh, ow, float(ortho["min_alt"]), float(ortho["max_alt"]), chunk=args.val_chunk,
+                                       occupancy_grid=occ, radiometric=(k_img == args.n_images and ortho["images"][0].shape[-1] == 3))
+                    res = {k: v.cpu() for k, v in res.items()}
+                    res["geotransform"] = nadir_geotransform(oh, ow, ortho["scene_offset"], ortho["scene_scale"])
+                    path = args.ortho_out or os.path.join(args.logs_dir, args.exp_name, "ortho.pt")
+                    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                    torch.save(res, path)
+                    print(f"step={step} | ortho={path} | cells={int((res['count'] > 0).sum())}/{oh * ow}", flush=True)
                 if args.dump_params:                                        # replica-equality checks of the tests
                     torch.save(field.flat_params().detach().cpu(), f"{args.dump_params}.rank{rank}")
                 if torch.distributed.is_initialized():
