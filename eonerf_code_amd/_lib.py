@@ -44,6 +44,8 @@ MARCH_SYMBOLS = ["eonerf_march_version", "eonerf_march_workspace_bytes", "eonerf
 QUANTILE_SYMBOLS = ["eonerf_quantile_version", "eonerf_quantile_workspace_bytes", "eonerf_render_depth_quantiles"]
 # include/eonerf_ortho.h: the stateless true-orthophoto group (ortho.py): surface points, per-image gather, fusion
 ORTHO_SYMBOLS = ["eonerf_ortho_version", "eonerf_ortho_ground", "eonerf_ortho_gather", "eonerf_ortho_fuse"]
+# include/eonerf_pose.h: camera offset refinement (pose.py) -- the ray-origin gradient behind a render backward and its per-image sum
+POSE_SYMBOLS = ["eonerf_pose_version", "eonerf_origin_grad_scratch_bytes", "eonerf_render_origin_grad"]
 
 
 class EonerfRpc(C.Structure):
@@ -72,6 +74,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_march.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_quantile.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_ortho.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_pose.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -210,8 +213,12 @@ def lib():
     L.eonerf_ortho_ground.argtypes = [vp, i, vp, C.c_long, f3, f3, i, i, vp, vp]
     L.eonerf_ortho_gather.argtypes = [vp, C.c_long, C.POINTER(EonerfRpc), vp, i, i, i, f3, f3, vp, fp, vp, vp, vp, vp]
     L.eonerf_ortho_fuse.argtypes = [vp, vp, i, C.c_long, i, i, vp, vp, vp, vp]
+    L.eonerf_pose_version.restype = i
+    L.eonerf_origin_grad_scratch_bytes.restype = sz
+    L.eonerf_origin_grad_scratch_bytes.argtypes = [vp, i, i]
+    L.eonerf_render_origin_grad.argtypes = [vp, vp, vp, vp, i, i, vp, sz, vp, sz, vp, vp, vp]
     for name in (SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS + QUANTILE_SYMBOLS
-                 + ORTHO_SYMBOLS):
+                 + ORTHO_SYMBOLS + POSE_SYMBOLS):
         getattr(L, name)
     _lib = L
     return L

@@ -65,6 +65,9 @@ struct eonerf_ctx {
     // point, so that the collective's kernel finds a CU while they run (every large kernel here fills the CUs it is given)
     hipEvent_t exch_event = nullptr; int exch_cus = 0; bool exch_recorded = false;
     const void* pre_consumed_ws = nullptr;   // workspace of the training forward that consumed a presample record: its backward checks the ray digest
+    // include/eonerf_pose.h: the last render backward that completed -- what eonerf_render_origin_grad may read (the forward's path record
+    // in ws_pipe is spent by then); dropped by every call that writes a workspace, re-packs the weights or presamples
+    struct PoseRec { bool valid = false; const void* ws = nullptr; int n_rays = 0, flags = 0, n_samples = 0; bool pipe = false; } pose;
     bool full_ig_dirty = false;      // packed lazily: only a differentiable EONerfMLP.forward with an input gradient reads it
     int* enc_colmap = nullptr;       // [64] device: encoding slot -> reference column (or -1)
     int* dev_status = nullptr;       // STICKY device status word (watchdog bits of the pipelined backward, bit 8: a remote rank's fault);
@@ -99,7 +102,7 @@ struct ProfScope {      // brackets one kernel launch with events when profiling
 
 inline bool slabs_addressable(const eonerf_ctx* ctx, size_t p_cap) { return slab_blocks_addressable(ctx->bf16, p_cap); }
 // a call that writes `ws` ends what eonerf_presample left there
-inline void drop_presample(eonerf_ctx* ctx, const void* ws) { if (ctx->pre.valid && ctx->pre.ws == ws) ctx->pre.valid = false; }
+inline void drop_presample(eonerf_ctx* ctx, const void* ws) { if (ctx->pre.valid && ctx->pre.ws == ws) ctx->pre.valid = false; ctx->pose.valid = false; }
 // rays per call: n_rays x (n_samples - 1) samples must stay below 2^31
 inline bool rays_in_range(const eonerf_ctx* ctx, int n_rays) { return n_rays <= (1 << 24) / (ctx->n_samples > 128 ? ctx->n_samples / 128 : 1); }
 // grid of the chain kernels (eonerf_mlp_fwd.hip, eonerf_mlp_bwd.hip): persistent workgroups, one per CU, never more than sample tiles

@@ -354,6 +354,7 @@ int eonerf_param_info(const eonerf_ctx* ctx, int index, const char** name, size_
 int eonerf_set_weights(eonerf_ctx* ctx, const float* flat, void* stream) {
     if (!ctx || !flat) return EONERF_E_ARG;
     hipStream_t st = (hipStream_t)stream;
+    ctx->pose.valid = false;
     // pipelined backward: the camera pass reads the heads-only streams + the stage-stationary trunk weights; the density-only streams
     // ride along when something has read them since the last re-pack (shadow pass on: they would be re-packed a few kernels later anyway)
     std::vector<const DevStream*> v;

@@ -182,7 +182,7 @@ int eonerf_render_depth_quantiles(eonerf_ctx* ctx, const float* flat, const floa
     const QuantileWs w = carve_quantile(carve_cfg(ctx), ws, n_rays, march ? block : 0);
     if (ws_bytes < w.bytes) return EONERF_E_WORKSPACE;
     if (ctx->need_repack) { const int rcr = eonerf_set_weights(ctx, flat, stream); if (rcr) return rcr; }
-    ctx->pre.valid = false;      // dropped: this call's kernels write the workspace the record described (or the caller moved on)
+    ctx->pre.valid = false; ctx->pose.valid = false;      // dropped: this call's kernels write the workspace the record described (or the caller moved on)
     qa.n_q = n_q; qa.out = out;
 
     if (!march) {

@@ -188,7 +188,7 @@ int eonerf_set_n_samples(eonerf_ctx* ctx, int n_samples) {
 
 int eonerf_set_noise_seed(eonerf_ctx* ctx, uint64_t seed) {
     if (!ctx) return EONERF_E_ARG;
-    ctx->noise_seed = seed; ctx->noise_call = 0; ctx->pre.valid = false;
+    ctx->noise_seed = seed; ctx->noise_call = 0; ctx->pre.valid = false; ctx->pose.valid = false;
     return EONERF_OK;
 }
 
@@ -279,6 +279,7 @@ int eonerf_rendering_backward(eonerf_ctx* ctx, const float* flat, const float* r
     if (!depth_only && !img_idx) return EONERF_E_ARG;
     if (!ctx->weights_set) return EONERF_E_STATE;
     if (!rays_in_range(ctx, n_rays) || !slabs_addressable(ctx, (size_t)p_cap_of(n_rays, ctx->n_samples))) return EONERF_E_UNSUPPORTED;      // (the forward's own bounds)
+    ctx->pose.valid = false;
     PipeModeGuard mode(ctx, ws);
     const int flags = EONERF_F_TRAIN | (depth_only ? EONERF_F_ONLY_DEPTH : 0);
     RenderWs w = carve_render(ctx, ws, n_rays, flags);
@@ -299,7 +300,7 @@ int eonerf_presample(eonerf_ctx* ctx, const float* rays, const int64_t* img_idx,
     hipStream_t st = (hipStream_t)stream;
     if (!ctx || !rays || !img_idx || !zsteps || n_rays < 0 || !ws) return EONERF_E_ARG;
     if (!(flags & EONERF_F_TRAIN) || (flags & EONERF_F_ONLY_DEPTH)) return EONERF_E_STATE;
-    ctx->pre.valid = false;
+    ctx->pre.valid = false; ctx->pose.valid = false;
     if (n_rays == 0) return EONERF_OK;
     if (!rays_in_range(ctx, n_rays) || !slabs_addressable(ctx, (size_t)p_cap_of(n_rays, ctx->n_samples))) return EONERF_E_UNSUPPORTED;
     RenderWs w = carve_render(ctx, ws, n_rays, flags);
@@ -331,6 +332,7 @@ int eonerf_render_forward(eonerf_ctx* ctx, const float* flat, const float* rays,
     hipStream_t st = (hipStream_t)stream;
     if (!ctx || !flat || !rays || !img_idx || !zsteps || !out || n_rays < 0 || !ws) return EONERF_E_ARG;
     if (!ctx->weights_set) return EONERF_E_STATE;
+    ctx->pose.valid = false;
     if (n_rays == 0) return EONERF_OK;
     if (ctx->need_repack) { const int rcr = eonerf_set_weights(ctx, flat, stream); if (rcr) return rcr; }
     const bool shadows = (flags & EONERF_F_SHADOWS) && !(flags & EONERF_F_ONLY_DEPTH);
@@ -401,6 +403,7 @@ static int render_backward_impl(eonerf_ctx* ctx, const float* flat, const float*
                                 void* ws, size_t ws_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     int refusal;
+    if (ctx) ctx->pose.valid = false;
     if (render_backward_refused(ctx, flat, rays, img_idx, n_rays, flags, d_flat, ws, ws_bytes, true, &refusal)) return refusal;
     PipeModeGuard mode(ctx, ws);
     const bool shadows = flags & EONERF_F_SHADOWS;
@@ -483,6 +486,10 @@ static int render_backward_impl(eonerf_ctx* ctx, const float* flat, const float*
                                     shadows ? &w.sun : nullptr, false, st, chk ? digest : nullptr, sun_enc_done);
     // (chain + GEMM path: the trunk's gradients come out of the GEMM launch -- the early block is final where everything is)
     if (!rcc && ctx->exch_event && !ctx->exch_recorded) HIP_TRY(hipEventRecord(ctx->exch_event, st));
+    if (!rcc) {      // (ctx->pipe is the forward's path here: PipeModeGuard)
+        ctx->pose.valid = true; ctx->pose.ws = ws; ctx->pose.n_rays = n_rays; ctx->pose.flags = flags; ctx->pose.n_samples = ctx->n_samples;
+        ctx->pose.pipe = ctx->pipe && w.pipe.dy_in;
+    }
     return rcc;
 }
 

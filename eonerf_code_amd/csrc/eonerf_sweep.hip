@@ -44,7 +44,7 @@ int eonerf_render_sun_sweep(eonerf_ctx* ctx, const float* flat, const float* ray
     const RenderWs& w = s.r;
     const int p_cap = p_cap_of(n_rays, ctx->n_samples);
     const int fwd_flags = (flags & EONERF_F_EVAL) | EONERF_F_SHADOWS;
-    ctx->pre.valid = false;      // dropped: this call's kernels write the workspace the record described (or the caller moved on)
+    ctx->pre.valid = false; ctx->pose.valid = false;      // dropped: this call's kernels write the workspace the record described (or the caller moved on)
 
     // ---- camera pass, once: sample -> field.  Its sampler reads columns 0..6 of the table only ----------------
     SampleArgs sa = camera_sample_args(ctx, w, rays, img_idx, zsteps, u_cam, u_retry, n_rays, n_samples_dev, true);      // (honours the context's occupancy grid)

@@ -80,12 +80,17 @@ def main():
     ap.add_argument("--dsm_quantile", type=float, default=None, help="val/mae and val/img_mae read the depth at this opacity quantile (0.5: the median surface) instead of the expected depth")
     ap.add_argument("--ortho", default=None, help="torch file with the input images, their RPCs, the mosaic size and the scene normalisation: true orthophoto after the last step")
     ap.add_argument("--ortho_out", default=None, help="where rank 0 saves the orthophoto (default: <logs_dir>/<exp_name>/ortho.pt)")
+    ap.add_argument("--rpc_correction", action="store_true", help="learn a 3-D offset per image, added to that image's ray origins (opt.py:80); single process only")
+    ap.add_argument("--rpc_lr", type=float, default=None, help="learning rate of the offsets (default: --lr)")
+    ap.add_argument("--resume", default=None, help="checkpoint to continue from (weights, optimizer state and, with --rpc_correction, the offsets)")
     args = ap.parse_args()
 
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     # EONERF_DP_REHEARSAL=1 (tests on a one-GPU box, not a deployment mode): every rank on cuda:0, gloo instead of RCCL; run it with
     # EONERF_PIPE=0 -- the pipelined backward assumes the card to itself
     rehearsal = os.environ.get("EONERF_DP_REHEARSAL") == "1"
+    if args.rpc_correction and world > 1:
+        raise SystemExit("--rpc_correction: the offsets are not exchanged between ranks yet; run it on one GPU (WORLD_SIZE=1)")
     if rehearsal:
         local = 0
     torch.cuda.set_device(local)
@@ -99,7 +104,7 @@ def main():
         else:
             torch.distributed.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
-    from .checkpoint import save_checkpoint
+    from .checkpoint import load_checkpoint, save_checkpoint
     from .radiance_fields.eonerf import EONerfMLP
     from .synthetic import synthetic_batch
     from .trainer import FusedTrainer, RayTable
@@ -125,7 +130,8 @@ def main():
     w_depth, depth_term = args.w_depth, [None]
     table = RayTable(rays, ts, rgbs, dev, seed=42, rank=rank, world=world, extras=extras)
     field = EONerfMLP(args.n_images, radiometric_normalization=True, precision=args.precision).to(dev)
-    trainer = FusedTrainer(field, lr=args.lr, max_rays=args.batch_size, keep_message=False, n_samples=args.n_samples)
+    trainer = FusedTrainer(field, lr=args.lr, max_rays=args.batch_size, keep_message=False, n_samples=args.n_samples,
+                           origin_offsets=args.rpc_correction, offsets_lr=args.rpc_lr)
     trainer.set_noise_seed(42 + 1000003 * rank)                              # per-rank jitter stream
     steps_per_epoch = max(1, table.steps_per_epoch(args.batch_size))
     occ = None
@@ -151,14 +157,22 @@ def main():
                 if key not in im:
                     raise SystemExit(f"--val_images {args.val_images}: image {k}: missing entry '{key}'")
         if rank == 0:
+            # "img_idx" (optional): the image's row of the offset table -- with --rpc_correction its rays are corrected before validation
             val_images = [{"rays": im["rays"].to(dev, torch.float32), "rgbs": im["rgbs"].to(dev, torch.float32), "h": int(im["h"]),
-                           "w": int(im["w"])} for im in v["images"][:max(0, args.val_max)]]
+                           "w": int(im["w"]), "img_idx": (int(im["img_idx"]) if im.get("img_idx") is not None else None)}
+                          for im in v["images"][:max(0, args.val_max)]]
     ortho = None
     if args.ortho:
         ortho = torch.load(args.ortho, map_location="cpu")
         for key in ("images", "rpcs", "size", "min_alt", "max_alt", "scene_offset", "scene_scale", "zone", "south"):
             if key not in ortho:
                 raise SystemExit(f"--ortho {args.ortho}: missing entry '{key}'")
+    pose_field = ""
+    if args.resume:
+        load_checkpoint(args.resume, field, trainer, occ_grid=occ)
+        if args.rpc_correction and rank == 0:
+            from .pose import max_offset
+            print(f"resumed={args.resume} | pose/max_offset={float(max_offset(trainer.origin_offsets)):.6g}", flush=True)
     step, tic = 0, time.time()
     for epoch in range(10 ** 7):
         for i in range(steps_per_epoch):
@@ -182,15 +196,19 @@ def main():
             if step % args.check_every == 0 and rank == 0:
                 el = time.time() - tic
                 prior_fields = "" if extras is None else f" | train/depth_l2={float(depth_term[0]):.5f} | depth_weight={w_depth:.6g}"
+                if args.rpc_correction:                                     # largest row norm in scene units: a drifting gauge shows here
+                    from .pose import max_offset
+                    pose_field = f" | pose/max_offset={float(max_offset(trainer.origin_offsets)):.6g}"
                 print(f"epoch={epoch} | elapsed_time={el:.2f}s | step={step} | loss={float(loss):.5f} | "
-                      f"rays/s={(step + 1) * args.batch_size * world / max(el, 1e-9):.0f}{prior_fields}", flush=True)
+                      f"rays/s={(step + 1) * args.batch_size * world / max(el, 1e-9):.0f}{prior_fields}{pose_field}", flush=True)
             save_now = step > 0 and step % (4 * steps_per_epoch) == 0         # save_freq, :180-191 (the same decision on every rank)
             if save_now and step % args.check_every != 0:
                 # a checkpoint must not hold updates that were skipped: after a device-side fault the Adam kernel leaves the weights alone
                 # while the host's step count keeps running -- every rank checks (and raises together) BEFORE rank 0 writes
                 trainer.check_device_status()
             if save_now and rank == 0:
-                save_checkpoint(os.path.join(args.logs_dir, args.exp_name, f"ckpts/epoch={epoch}.ckpt"), epoch, field, trainer, loss, occ_grid=occ)
+                save_checkpoint(os.path.join(args.logs_dir, args.exp_name, f"ckpts/epoch={epoch}.ckpt"), epoch, field, trainer, loss, occ_grid=occ,
+                                origin_offsets=trainer if args.rpc_correction else None)
             if step == args.max_train_steps:
                 trainer.check_device_status()
                 if ortho is not None and rank == 0:
@@ -227,7 +245,13 @@ def main():
                 trainer.check_device_status()                               # on every rank (with --gt_dsm the check above has just run)
             if rank == 0 and val_images:
                 from .validation import validate_images
-                _, means = validate_images(field, val_images, epoch, chunk=args.val_chunk, gt=gt, max_images=args.val_max, occupancy_grid=occ,
+                images = val_images
+                if args.rpc_correction:                                     # the tables whose image index is known render on corrected rays
+                    from .pose import apply_origin_offsets
+                    images = [im if im["img_idx"] is None else
+                              dict(im, rays=apply_origin_offsets(im["rays"], torch.full((im["rays"].shape[0],), im["img_idx"], dtype=torch.int64, device=dev),
+                                                                 trainer.origin_offsets)) for im in val_images]
+                _, means = validate_images(field, images, epoch, chunk=args.val_chunk, gt=gt, max_images=args.val_max, occupancy_grid=occ,
                                            early_stop_eps=args.early_stop_eps, march_block=args.march_block, depth_quantile=args.dsm_quantile)
                 names = ("loss", "coarse_color", "coarse_logbeta", "psnr") + (("mae",) if gt is not None else ())
                 vals = torch.stack([means[k] for k in names]).tolist()      # the validation's one read-back

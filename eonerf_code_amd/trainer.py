@@ -18,6 +18,7 @@ import os
 import torch
 
 from . import _lib
+from .pose import apply_origin_offsets, origin_grad
 from .radiance_fields.eonerf import EONerfMLP, _ptr, _stream
 from .sat_rendering import _zsteps
 
@@ -44,11 +45,17 @@ def rank_slice(n_total, rank, world):
 
 class FusedTrainer:
     def __init__(self, field: EONerfMLP, lr: float = 5e-4, betas=(0.9, 0.999), eps: float = 1e-8, max_rays: int = 4096,
-                 keep_message: bool = True, n_samples: int = 128):
+                 keep_message: bool = True, n_samples: int = 128, origin_offsets: bool = False, offsets_lr: float = None):
         """keep_message=True: the gradient message survives the update (d_flat can be read after step()) and is sealed with the
         fault flag even when there are no peers -- what tests and debugging want.  The launcher and bench.py pass False: the update
         consumes the message (eonerf_adam_step_zero_grad: optimizer.step() + the next optimizer.zero_grad(), train_eonerf.py:158-161,
-        in one kernel) and a single process skips the seal (k_adam reads the status word itself): two launches fewer per step."""
+        in one kernel) and a single process skips the seal (k_adam reads the status word itself): two launches fewer per step.
+        origin_offsets=True (the reference's --rpc_correction): the trainer owns self.origin_offsets, a zero [n_images, 3] table of
+        per-image camera offsets, renders every batch on pose.apply_origin_offsets(rays, img_idx, self.origin_offsets), takes the
+        ray-origin gradient behind the backward (include/eonerf_pose.h) and steps the table with a plain torch.optim.Adam at offsets_lr
+        (default: lr).  The presampler is not used (the next batch's origins depend on this step's update).  Single process only."""
+        if origin_offsets and torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise NotImplementedError("origin_offsets=True at world size > 1: the offsets' all-reduce is not implemented")
         self.field = field
         self.keep_message = keep_message
         self.tail_events = None      # a list: reduce_and_update() appends an event pair around the exchange + update (bench.py, N > 1)
@@ -92,12 +99,24 @@ class FusedTrainer:
         self.zsteps = _zsteps(dev, self.n_samples_per_ray)
         self.n_early = int(self.L.eonerf_grad_early_floats(self.ctx))
         self.set_exchange_buckets(self.buckets)
+        self.origin_offsets = self.d_offsets = self.offsets_opt = None
+        if origin_offsets:
+            self.origin_offsets = torch.zeros(field.n_input_images, 3, dtype=torch.float32, device=dev)
+            self.d_offsets = torch.zeros_like(self.origin_offsets)
+            self.origin_offsets.grad = self.d_offsets
+            self.offsets_opt = torch.optim.Adam([self.origin_offsets], lr=lr if offsets_lr is None else offsets_lr,
+                                                betas=betas, eps=eps)
+            self._offsets_lr_own = offsets_lr is not None
         if self.world > 1:     # identical replicas: broadcast rank 0's parameters once (train_eonerf.py has one process)
             torch.distributed.broadcast(self.flat, src=0)
             _lib.check(self.L.eonerf_set_weights(self.ctx, _ptr(self.flat), _stream()))
 
     def set_lr(self, lr):
         """StepLR(gamma=0.9) is applied by the caller once per epoch (train_eonerf.py:64,304)."""
+        if self.offsets_opt is not None:      # the offsets follow the same schedule: their rate keeps its ratio to the field's
+            old = self.lr
+            for g in self.offsets_opt.param_groups:
+                g["lr"] = g["lr"] * (lr / old) if (self._offsets_lr_own and old) else lr
         self.lr = lr
 
     def _workspace(self, n, flags):
@@ -162,6 +181,8 @@ class FusedTrainer:
             # the presampled record is not for THESE tensors as they are now (other batch, or the same buffers refilled in place): drop it,
             # the forward samples itself.  (What torch cannot see -- a raw-pointer write -- the library's device-side digest catches.)
             _lib.check(self.L.eonerf_presample_cancel(self.ctx))
+        if self.origin_offsets is not None:      # forward, backward and the origin gradient all see the corrected table
+            rays = apply_origin_offsets(rays, img_idx, self.origin_offsets)
         self._render_forward(rays, img_idx, n, flags, (u_cam, u_retry, u_sun))
         if aux_loss is not None:
             loss = self.loss_grad(self.out[:n], pixels.contiguous(), epoch_idx, self.d_out)
@@ -197,7 +218,11 @@ class FusedTrainer:
         else:
             _lib.check(self.L.eonerf_render_backward(self.ctx, _ptr(self.flat), _ptr(rays), _ptr(img_idx), n, flags, _ptr(self.d_out),
                                                      _ptr(self.d_flat), _ptr(ws), ws.numel(), st))
-        if self.keep_message or self._exchanges():     # the flag travels with the message; alone, k_adam reads the status word itself
+        if self.origin_offsets is not None:      # directly behind the backward, on its workspace (every loss path ends here)
+            self.d_offsets.zero_()
+            origin_grad(self.ctx, self.flat, rays, img_idx, flags, ws, d_offsets=self.d_offsets)
+        # the flag travels with the message; alone, k_adam reads the status word itself (the offsets' update reads the sealed flag)
+        if self.keep_message or self._exchanges() or self.origin_offsets is not None:
             _lib.check(self.L.eonerf_grad_seal(self.ctx, _ptr(self.d_flat), st))
 
     def set_exchange_buckets(self, n):
@@ -228,6 +253,9 @@ class FusedTrainer:
         if tail is not None:      # bench.py at N > 1: the serial tail of a step (exchange + update + re-pack) between two events
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
+        if self.origin_offsets is not None:
+            next_batch = None      # accepted and ignored: the next batch's origins depend on this step's update
+            self._step_offsets()
         gscale = self._reduce(st, next_batch)
         self.step_count += 1
         flag = C.c_void_p(self.d_flat.data_ptr() + 4 * self.n_params) if (self.keep_message or self._exchanges()) else None
@@ -241,6 +269,21 @@ class FusedTrainer:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record()
             tail.append((e0, e1))
+
+    def _step_offsets(self):
+        """torch Adam on the offset table, undone ON THE DEVICE when the gradient message carries the fault flag -- the flag the field's
+        own update is skipped by (eonerf_grad_seal wrote it from the context's status word): no host synchronisation.  Like the field's,
+        the optimizer's step COUNT runs on through a skipped step."""
+        bad = self.d_flat[self.n_params:self.n_params + 1] != 0
+        st = self.offsets_opt.state.get(self.origin_offsets, {})
+        kept = [(self.origin_offsets, self.origin_offsets.clone())] + [(st[k], st[k].clone()) for k in ("exp_avg", "exp_avg_sq") if k in st]
+        self.offsets_opt.step()
+        st = self.offsets_opt.state[self.origin_offsets]
+        for t, old in kept:
+            t.copy_(torch.where(bad, old, t))
+        if len(kept) == 1:      # the very first step created the moments: a skipped step leaves them at zero
+            for k in ("exp_avg", "exp_avg_sq"):
+                st[k].mul_((~bad).to(st[k].dtype))
 
     def _presample(self, rays, img_idx, epoch_idx, with_aux_loss=False):
         n = rays.shape[0]
