@@ -46,6 +46,9 @@ QUANTILE_SYMBOLS = ["eonerf_quantile_version", "eonerf_quantile_workspace_bytes"
 ORTHO_SYMBOLS = ["eonerf_ortho_version", "eonerf_ortho_ground", "eonerf_ortho_gather", "eonerf_ortho_fuse"]
 # include/eonerf_pose.h: camera offset refinement (pose.py) -- the ray-origin gradient behind a render backward and its per-image sum
 POSE_SYMBOLS = ["eonerf_pose_version", "eonerf_origin_grad_scratch_bytes", "eonerf_render_origin_grad"]
+# include/eonerf_normals.h: the forward-mode density gradient and the surface normals of export renders (normals.py)
+NORMALS_SYMBOLS = ["eonerf_normals_version", "eonerf_density_grad_workspace_bytes", "eonerf_field_density_grad",
+                   "eonerf_normals_workspace_bytes", "eonerf_render_normals"]
 
 
 class EonerfRpc(C.Structure):
@@ -75,6 +78,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_quantile.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_ortho.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_pose.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_normals.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -217,8 +221,15 @@ def lib():
     L.eonerf_origin_grad_scratch_bytes.restype = sz
     L.eonerf_origin_grad_scratch_bytes.argtypes = [vp, i, i]
     L.eonerf_render_origin_grad.argtypes = [vp, vp, vp, vp, i, i, vp, sz, vp, sz, vp, vp, vp]
+    L.eonerf_normals_version.restype = i
+    L.eonerf_density_grad_workspace_bytes.restype = sz
+    L.eonerf_density_grad_workspace_bytes.argtypes = [vp, i]
+    L.eonerf_field_density_grad.argtypes = [vp, vp, vp, i, vp, vp, vp, sz, vp]
+    L.eonerf_normals_workspace_bytes.restype = sz
+    L.eonerf_normals_workspace_bytes.argtypes = [vp, i]
+    L.eonerf_render_normals.argtypes = [vp, vp, vp, vp, vp, vp, i, f3, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     for name in (SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS + QUANTILE_SYMBOLS
-                 + ORTHO_SYMBOLS + POSE_SYMBOLS):
+                 + ORTHO_SYMBOLS + POSE_SYMBOLS + NORMALS_SYMBOLS):
         getattr(L, name)
     _lib = L
     return L

@@ -319,8 +319,9 @@ template <int KG> EO_DEV constexpr int slice_pos(int s) { return KG >= 14 ? 5 + 
 
 // `last`: the accumulator of the chunk's LAST m-tile is handed back with its epilogue still to run (run_layer places it in front of or
 // behind the chunk barrier, see there).
-template <class P, int KG, int G, bool BIAS, class WS, class BArr, class Epi, class Mid>
-EO_DEV void chunk_compute(WS& ws, int lane, int h, const BArr& B, int m0, Epi&& epi, Mid&& mid, f32x16& last) {
+// (`h` only selects the bias rows: the lane's half -- or a type with a bias_init overload of its own, eonerf_normals.hip)
+template <class P, int KG, int G, bool BIAS, class WS, class HSel, class BArr, class Epi, class Mid>
+EO_DEV void chunk_compute(WS& ws, int lane, HSel h, const BArr& B, int m0, Epi&& epi, Mid&& mid, f32x16& last) {
     const uint8_t* chunk = ws.cur();
     // prefetch rounds are issued after MFMAs 0, 1, 2, ... of the first m-tile (early: the copy has to land within the chunk);
     // the last position takes what is left
@@ -386,8 +387,8 @@ EO_DEV void chunk_compute(WS& ws, int lane, int h, const BArr& B, int m0, Epi&& 
 
 // A whole layer: MT m-tiles in n_groups(KG, MT) chunks.  NST = slab stores every m-tile's epilogue issues (lower bound, 0 = unknown).
 // `mid` provides the slab-flush hooks called a few MFMAs into every m-tile (or no-ops).
-template <class P, int SLOT, int KG, int MT, bool BIAS, int NST = 0, int C = 0, class Mid, class BArr, class Epi>
-EO_DEV void run_layer(WStream<P, SLOT>& ws, Mid&& mid, int lane, int h, const BArr& B, Epi&& epi) {
+template <class P, int SLOT, int KG, int MT, bool BIAS, int NST = 0, int C = 0, class Mid, class HSel, class BArr, class Epi>
+EO_DEV void run_layer(WStream<P, SLOT>& ws, Mid&& mid, int lane, HSel h, const BArr& B, Epi&& epi) {
     constexpr int TG = chunk_target<P>();
     if constexpr (C < n_groups(KG, MT, TG)) {
         constexpr int G = group_size(KG, MT, C, TG), M0 = group_start(KG, MT, C, TG);

@@ -192,15 +192,18 @@ class EONerfMLP(nn.Module):
         except Exception:
             pass
 
-    def _native(self, export=False):
+    def _native(self, export=False, no_bf16=False):
         """(context, flat parameters) to run a call on, packed weights up to date.  export=True on a bf16 module with
-        eval_precision "fp16x3" / "fp32": the module's second context, of that precision, over the SAME flat parameter buffer."""
-        if not (export and self.precision == "bf16" and self.eval_precision != "same"):
+        eval_precision "fp16x3" / "fp32": the module's second context, of that precision, over the SAME flat parameter buffer.
+        no_bf16 (with export): the call has no bf16 form (normals.py) -- a bf16 module with eval_precision "same", whose second
+        context nobody else uses, gets an fp32 one there."""
+        if not (export and self.precision == "bf16" and (self.eval_precision != "same" or no_bf16)):
             return self._context(), self._ensure_packed()
         flat = self.flat_params()
         L = _lib.lib()
         if self._ctx_eval is None:
-            cfg = _lib.EonerfConfig(self.n_input_images, _lib.PRECISIONS[self.eval_precision], self._n_samples, 1 if self.radiometric_normalization else 0)
+            prec = "fp32" if self.eval_precision == "same" else self.eval_precision
+            cfg = _lib.EonerfConfig(self.n_input_images, _lib.PRECISIONS[prec], self._n_samples, 1 if self.radiometric_normalization else 0)
             ctx = C.c_void_p()
             _lib.check(L.eonerf_create(C.byref(ctx), C.byref(cfg)))
             self._ctx_eval = ctx

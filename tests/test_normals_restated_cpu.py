@@ -1,0 +1,139 @@
+"""CPU: the four-plane density chain and the normal compositing of include/eonerf_normals.h restated (tests/normals_restated.py), held
+to torch.autograd of the oracle in fp64, and the binding's symbol list against the new header.
+
+Kept points.  The gradient of a ReLU network is discontinuous at a kink, so a comparison across one shows nothing: a point is used when
+the fp64 minimum |pre-activation| over the eight trunk layers exceeds 1e-5.  On the seeded field below 6.98 % of the 2,048 points are
+left out; the test allows 10 %."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import REPO
+from oracle import eonerf_oracle as orc
+import normals_restated as nr
+
+
+def seeded_sd():
+    return orc.random_state_dict(3, seed=42, bias_scale=0.1)
+
+
+def cube_points(n=2048):
+    return torch.rand(n, 3, generator=torch.Generator().manual_seed(7)) * 2 - 1
+
+
+def oracle_gradient(sd, x, dtype):
+    """(sigma [n], d sigma / d x [n, 3]) by torch.autograd of the oracle's query_density in `dtype`."""
+    sdt = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
+    xx = x.to(dtype).clone().requires_grad_(True)
+    sigma = orc.Field(sdt).query_density(xx)
+    g, = torch.autograd.grad(sigma.sum(), xx)
+    return sigma.detach().reshape(-1).numpy(), g.numpy()
+
+
+def test_restated_forward_mode_gradient_is_autograd_of_the_oracle_in_fp64():
+    sd, x = seeded_sd(), cube_points()
+    sigma, grad, min_pre = nr.density_planes(sd, x.double().numpy())
+    keep = nr.kept(min_pre)
+    left_out = 1.0 - keep.mean()
+    print(f"left out: {100 * left_out:.2f} % of {len(keep)} points")
+    assert left_out <= 0.10
+    s64, g64 = oracle_gradient(sd, x, torch.float64)
+    assert np.abs(sigma - s64).max() <= 1e-10 * np.abs(s64).max()
+    mx, l2 = nr.rel_stats(grad[keep], g64[keep])
+    print(f"restated vs fp64 autograd: max relative {mx:.2e}, relative L2 {l2:.2e}")
+    assert mx <= 1e-10 and l2 <= 1e-10
+    # the yardstick of the device tests: the oracle's own fp32 autograd on the same points
+    _, g32 = oracle_gradient(sd, x, torch.float32)
+    mx32, l232 = nr.rel_stats(g32[keep], g64[keep])
+    print(f"oracle fp32 autograd vs fp64: max relative {mx32:.2e}, relative L2 {l232:.2e}")
+    assert mx32 < 1e-3 and l232 < 1e-4      # no kink flip among the kept points (a flip is an error of order 0.1)
+
+
+def test_encoding_planes_are_the_derivative_of_the_encoding():
+    x = cube_points(16).double().numpy()
+    E = nr.encode_planes(x)
+    h = 1e-6
+    for j in range(3):
+        dx = np.zeros(3)
+        dx[j] = h
+        fd = (nr.encode_planes(x + dx)[:, 0] - nr.encode_planes(x - dx)[:, 0]) / (2 * h)
+        assert np.abs(fd - E[:, 1 + j]).max() <= 1e-6 * 512
+    ref = orc.sinusoidal_encode(torch.from_numpy(x), 10).numpy()
+    assert np.abs(ref - E[:, 0]).max() <= 1e-15 * 512
+
+
+# ---- compositing ----------------------------------------------------------------------------------------------------------------------
+def test_a_single_sample_ray_gives_minus_w_u():
+    g = np.array([[3.0, 0.0, -4.0]])
+    depth, N, A = nr.composite([2.0], [0.25], [0.7], g)
+    w = 1.0 - np.exp(-0.5)
+    assert A == pytest.approx(w, rel=1e-15) and depth == pytest.approx(0.7 * w, rel=1e-15)
+    assert N == pytest.approx(-w * np.array([0.6, 0.0, -0.8]), rel=1e-15)
+
+
+def test_a_zero_or_non_finite_gradient_contributes_nothing_to_N_but_counts_in_A():
+    sigma, delta, mid = [1.0, 2.0, 3.0], [0.1, 0.1, 0.1], [0.1, 0.2, 0.3]
+    g = np.array([[0.0, 0.0, 1.0], [0.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
+    _, N, A = nr.composite(sigma, delta, mid, g)
+    w = nr.ray_weights(sigma, delta)
+    assert N == pytest.approx([0.0, -w[2], -w[0]], rel=1e-15) and A == pytest.approx(w.sum(), rel=1e-15)
+    for bad in (np.nan, np.inf):
+        g2 = g.copy()
+        g2[1] = [bad, 1.0, 1.0]
+        assert nr.composite(sigma, delta, mid, g2)[1] == pytest.approx(N, rel=1e-15)
+    assert nr.composite([], [], [], np.zeros((0, 3))) == (0.0, pytest.approx(np.zeros(3)), 0.0)
+
+
+def test_norm_of_N_is_at_most_A_is_at_most_one():
+    rng = np.random.default_rng(11)
+    for _ in range(100):
+        n = int(rng.integers(1, 128))
+        sigma = rng.random(n) * (rng.random(n) < 0.5) * 30.0
+        ts = np.sort(rng.random(n + 1)).astype(np.float32)
+        delta = nr.last_delta(ts[:-1], ts[1:])
+        g = rng.standard_normal((n, 3)) * 10.0 ** rng.integers(-3, 4, (n, 1))
+        _, N, A = nr.composite(sigma, delta, 0.5 * (ts[:-1] + ts[1:]), g)
+        assert np.linalg.norm(N) <= A * (1 + 1e-12) and A <= 1.0 + 1e-12
+    # agreeing samples reach the bound, opposing ones cancel
+    same = np.tile([[0.0, 0.0, -2.0]], (5, 1))
+    _, N, A = nr.composite(np.full(5, 4.0), np.full(5, 0.1), np.arange(5), same)
+    assert N == pytest.approx([0.0, 0.0, A], rel=1e-15)
+
+
+def test_axis_scale_acts_before_the_normalisation():
+    g = np.array([[1.0, 0.0, 1.0]])
+    _, N, A = nr.composite([5.0], [1.0], [0.0], g, axis_scale=(1.0, 1.0, 0.5))
+    assert N == pytest.approx(-A * np.array([2.0, 0.0, 1.0]) / np.sqrt(5.0), rel=1e-15)      # not (1, 0, 0.5) / sqrt(2)
+    u = nr.unit_gradients(g, (1.0, 1.0, 0.5))
+    assert np.linalg.norm(u) == pytest.approx(1.0, rel=1e-15)
+
+
+def test_restatement_imports_nothing_from_the_product_path():
+    src = open(os.path.join(REPO, "tests", "normals_restated.py")).read()
+    assert re.findall(r"^\s*(?:import|from)\s+(\S+)", src, flags=re.M) == ["numpy"]
+
+
+# ---- header pins ------------------------------------------------------------------------------------------------------------------
+def test_normals_header_symbols_are_bound_and_exported():
+    from eonerf_code_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    hdr = open(os.path.join(REPO, "include", "eonerf_normals.h")).read()
+    declared = set(re.findall(r"\b(eonerf_[a-z_]+)\s*\(", hdr))
+    assert declared == set(_lib.NORMALS_SYMBOLS) and len(declared) == 5
+    assert not set(_lib.NORMALS_SYMBOLS) & set(_lib.SYMBOLS)
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    for name in declared:
+        assert hasattr(L, name), name
+    L.eonerf_normals_version.restype = ctypes.c_int
+    assert L.eonerf_normals_version() == 1
+    assert int(re.search(r"#define\s+EONERF_NORMALS_VERSION\s+(\d+)", hdr).group(1)) == 1
+    L.eonerf_version.restype = ctypes.c_int
+    assert L.eonerf_version() == 502
+    L.eonerf_normals_workspace_bytes.restype = ctypes.c_size_t
+    L.eonerf_density_grad_workspace_bytes.restype = ctypes.c_size_t
+    assert L.eonerf_normals_workspace_bytes(None, 1) == 0 and L.eonerf_density_grad_workspace_bytes(None, 1) == 0
