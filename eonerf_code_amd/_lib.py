@@ -49,6 +49,8 @@ POSE_SYMBOLS = ["eonerf_pose_version", "eonerf_origin_grad_scratch_bytes", "eone
 # include/eonerf_normals.h: the forward-mode density gradient and the surface normals of export renders (normals.py)
 NORMALS_SYMBOLS = ["eonerf_normals_version", "eonerf_density_grad_workspace_bytes", "eonerf_field_density_grad",
                    "eonerf_normals_workspace_bytes", "eonerf_render_normals"]
+# include/eonerf_mesh.h: the stateless mesh export group (mesh.py) -- marching tetrahedra over a sampled density volume
+MESH_SYMBOLS = ["eonerf_mesh_version", "eonerf_mesh_lattice_points", "eonerf_mesh_workspace_bytes", "eonerf_mesh_count", "eonerf_mesh_emit"]
 
 
 class EonerfRpc(C.Structure):
@@ -79,6 +81,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_ortho.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_pose.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_normals.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_mesh.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -228,8 +231,14 @@ def lib():
     L.eonerf_normals_workspace_bytes.restype = sz
     L.eonerf_normals_workspace_bytes.argtypes = [vp, i]
     L.eonerf_render_normals.argtypes = [vp, vp, vp, vp, vp, vp, i, f3, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.eonerf_mesh_version.restype = i
+    L.eonerf_mesh_lattice_points.argtypes = [f3, f3, i, i, i, i, vp, vp]
+    L.eonerf_mesh_workspace_bytes.restype = sz
+    L.eonerf_mesh_workspace_bytes.argtypes = [i, i, i]
+    L.eonerf_mesh_count.argtypes = [vp, i, i, i, fp, vp, vp, sz, vp]
+    L.eonerf_mesh_emit.argtypes = [vp, i, i, i, fp, f3, f3, vp, sz, vp, C.c_int64, vp, C.c_int64, vp, vp, vp]
     for name in (SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS + QUANTILE_SYMBOLS
-                 + ORTHO_SYMBOLS + POSE_SYMBOLS + NORMALS_SYMBOLS):
+                 + ORTHO_SYMBOLS + POSE_SYMBOLS + NORMALS_SYMBOLS + MESH_SYMBOLS):
         getattr(L, name)
     _lib = L
     return L

@@ -32,6 +32,11 @@ step itself never reads the grid.  Without the flag nothing changes.
 of the images on the nadir grid (eonerf_code_amd.ortho.orthorectify: the images gathered through their RPCs on the rendered surface,
 occluded cells left out, median-fused) and torch.saves the result dict plus "geotransform" to `--ortho_out`.  `--occ_grid` and the step
 size reach that render as they reach the validation renders.  Without the flag nothing changes.
+
+`--mesh_out PATH` writes, after the last step and on rank 0 only, a triangle mesh of the field's density level set as a binary PLY
+(eonerf_code_amd.mesh.extract_mesh / save_ply: marching tetrahedra on a `--mesh_res`^3 lattice over the normalised cube, per-vertex
+normals and albedo).  `--mesh_level` is the density of the level set; its default (half opacity over one render step of 128 samples) is
+a guess that has not been measured on a converged scene.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -80,6 +85,9 @@ def main():
     ap.add_argument("--dsm_quantile", type=float, default=None, help="val/mae and val/img_mae read the depth at this opacity quantile (0.5: the median surface) instead of the expected depth")
     ap.add_argument("--ortho", default=None, help="torch file with the input images, their RPCs, the mosaic size and the scene normalisation: true orthophoto after the last step")
     ap.add_argument("--ortho_out", default=None, help="where rank 0 saves the orthophoto (default: <logs_dir>/<exp_name>/ortho.pt)")
+    ap.add_argument("--mesh_out", default=None, help="where rank 0 saves a PLY mesh of the density level set after the last step")
+    ap.add_argument("--mesh_res", type=int, default=256, help="lattice points per axis of the mesh extraction")
+    ap.add_argument("--mesh_level", type=float, default=None, help="density of the extracted level set (default: mesh.level_from_opacity(0.5, 2 / 128))")
     ap.add_argument("--rpc_correction", action="store_true", help="learn a 3-D offset per image, added to that image's ray origins (opt.py:80); single process only")
     ap.add_argument("--rpc_lr", type=float, default=None, help="learning rate of the offsets (default: --lr)")
     ap.add_argument("--resume", default=None, help="checkpoint to continue from (weights, optimizer state and, with --rpc_correction, the offsets)")
@@ -224,6 +232,13 @@ def main():
                     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
                     torch.save(res, path)
                     print(f"step={step} | ortho={path} | cells={int((res['count'] > 0).sum())}/{oh * ow}", flush=True)
+                if args.mesh_out and rank == 0:
+                    from .mesh import extract_mesh, save_ply
+                    mesh = extract_mesh(field, resolution=args.mesh_res, level=args.mesh_level)
+                    os.makedirs(os.path.dirname(os.path.abspath(args.mesh_out)), exist_ok=True)
+                    save_ply(args.mesh_out, mesh)
+                    print(f"step={step} | mesh={args.mesh_out} | vertices={mesh['vertices'].shape[0]} | faces={mesh['faces'].shape[0]} | "
+                          f"level={mesh['level']:.6g}", flush=True)
                 if args.dump_params:                                        # replica-equality checks of the tests
                     torch.save(field.flat_params().detach().cpu(), f"{args.dump_params}.rank{rank}")
                 if torch.distributed.is_initialized():
