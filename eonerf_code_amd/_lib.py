@@ -51,6 +51,8 @@ NORMALS_SYMBOLS = ["eonerf_normals_version", "eonerf_density_grad_workspace_byte
                    "eonerf_normals_workspace_bytes", "eonerf_render_normals"]
 # include/eonerf_mesh.h: the stateless mesh export group (mesh.py) -- marching tetrahedra over a sampled density volume
 MESH_SYMBOLS = ["eonerf_mesh_version", "eonerf_mesh_lattice_points", "eonerf_mesh_workspace_bytes", "eonerf_mesh_count", "eonerf_mesh_emit"]
+# include/eonerf_components.h: connected components of a volume under the mesher's connectivity, and the floater / cavity filter (mesh.py)
+CC_SYMBOLS = ["eonerf_cc_version", "eonerf_cc_workspace_bytes", "eonerf_cc_label", "eonerf_cc_filter"]
 
 
 class EonerfRpc(C.Structure):
@@ -82,6 +84,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_pose.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_normals.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_mesh.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_components.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -237,8 +240,13 @@ def lib():
     L.eonerf_mesh_workspace_bytes.argtypes = [i, i, i]
     L.eonerf_mesh_count.argtypes = [vp, i, i, i, fp, vp, vp, sz, vp]
     L.eonerf_mesh_emit.argtypes = [vp, i, i, i, fp, f3, f3, vp, sz, vp, C.c_int64, vp, C.c_int64, vp, vp, vp]
+    L.eonerf_cc_version.restype = i
+    L.eonerf_cc_workspace_bytes.restype = sz
+    L.eonerf_cc_workspace_bytes.argtypes = [i, i, i]
+    L.eonerf_cc_label.argtypes = [vp, i, i, i, fp, i, vp, vp, vp, vp, sz, vp]
+    L.eonerf_cc_filter.argtypes = [vp, vp, vp, i, i, i, i, C.c_int64, i, vp, vp, vp]
     for name in (SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS + QUANTILE_SYMBOLS
-                 + ORTHO_SYMBOLS + POSE_SYMBOLS + NORMALS_SYMBOLS + MESH_SYMBOLS):
+                 + ORTHO_SYMBOLS + POSE_SYMBOLS + NORMALS_SYMBOLS + MESH_SYMBOLS + CC_SYMBOLS):
         getattr(L, name)
     _lib = L
     return L

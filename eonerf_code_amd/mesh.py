@@ -6,8 +6,15 @@ normals.density_gradient uses, so values and gradients of one mesh come from one
 bit-reproducible function of the volume (eonerf_mesh_count / eonerf_mesh_emit: classify, scan, emit; no vertex table, nothing welded).
 PyTorch owns the memory and the stream; the arithmetic runs in libeonerf_hip.so.
 
-Not here: marching cubes, vertex refinement along the gradient, floater filters, simplification and welding, textures, skipping empty
-space through the occupancy grid while the volume is filled, volumes larger than one call, OBJ / glTF writers.
+Mesh clean-up (include/eonerf_components.h) works on the volume in front of the extraction: label_components finds the solids the mesh
+encloses -- the connected components of the inside lattice points under the 14 edges of the mesher's own split -- or, on the outside,
+the cavities; filter_components drops solids below a point count or all but the k largest and fills cavities, element-wise, so that
+the mesh of the filtered volume is the mesh of the original one without those components, bit for bit; vertex_components gives every
+vertex the id of its solid.  Every filter is off by default: what a good min_points is on a converged scene has not been measured.
+
+Not here: marching cubes, vertex refinement along the gradient, filters on area or height above ground, labelling of the mesh graph
+itself, simplification and welding, textures, skipping empty space through the occupancy grid while the volume is filled, volumes larger
+than one call, OBJ / glTF writers.
 The default level of extract_mesh is a guess: it has not been measured on a converged scene, and neither has the quality of the mesh.
 """
 import ctypes as C
@@ -130,6 +137,105 @@ def mesh_from_volume(volume, level, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1
     return out + (keys[:n_v],) if return_keys else out
 
 
+SIDES = {"inside": 0, "outside": 1, 0: 0, 1: 1}
+BOUNDARY_BIT = 0x80000000
+COUNT_MASK = 0x7FFFFFFF
+ALL_POINTS = 1 << 29            # a min_points above every count (one call takes 2^28 points)
+SLOT_OFFSETS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))      # (dx, dy, dz) of the edge slots 0 .. 6
+
+
+def _volume3(volume):
+    if volume.dim() != 3 or volume.device.type != "cuda":
+        raise ValueError("volume must be a [nz, ny, nx] tensor on the GPU (the component group has no host form)")
+    vol = volume.detach().float().contiguous()
+    nz, ny, nx = vol.shape
+    if not _lib.lib().eonerf_cc_workspace_bytes(nx, ny, nz):
+        raise ValueError(f"a {nz} x {ny} x {nx} volume: every dimension must be at least 2 and one call takes 2^28 points")
+    return vol, nz, ny, nx
+
+
+def _label(vol, level, side):
+    """labels, info and the counts ON THE DEVICE (no read-back)."""
+    nz, ny, nx = vol.shape
+    L = _lib.lib()
+    dev = vol.device
+    nb = L.eonerf_cc_workspace_bytes(nx, ny, nz)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    labels = torch.empty(nz, ny, nx, dtype=torch.int32, device=dev)
+    info = torch.empty(nz, ny, nx, dtype=torch.int32, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    _lib.check(L.eonerf_cc_label(_ptr(vol), nx, ny, nz, float(level), side, _ptr(labels), _ptr(info), _ptr(counts), _ptr(ws), nb, _stream()))
+    return labels, info, counts
+
+
+def _filter(vol, labels, info, side, min_points, protect_boundary, out):
+    """eonerf_cc_filter into `out` (may be vol itself); the two dropped counts stay on the device."""
+    nz, ny, nx = vol.shape
+    dropped = torch.empty(2, dtype=torch.int64, device=vol.device)
+    _lib.check(_lib.lib().eonerf_cc_filter(_ptr(vol), _ptr(labels), _ptr(info), nx, ny, nz, side, int(min_points), int(bool(protect_boundary)),
+                                           _ptr(out), _ptr(dropped), _stream()))
+    return dropped
+
+
+@torch.no_grad()
+def label_components(volume, level, side="inside"):
+    """Connected components of one side of volume [nz, ny, nx] (fp32, on the device) by the rule of include/eonerf_components.h: inside
+    is volume >= level (a NaN is outside), two points are adjacent iff they differ by one of the seven edge directions of the mesher's
+    split or its negative -- so the inside components are exactly the solids mesh_from_volume encloses, and the outside components off
+    the volume's boundary its cavities.  Returns (labels int32 [nz, ny, nx]: the smallest linear index of the point's component, -1 off
+    the side; info int32 [nz, ny, nx]: at a root (labels[r] == r) the component's point count in bits 0 .. 30 and, in bit 31 (the sign),
+    whether it touches the volume's boundary, 0 elsewhere; dict of "components", "points", "largest", "largest_root").  One read-back."""
+    if side not in SIDES:
+        raise ValueError(f"side={side!r}: 'inside' or 'outside'")
+    vol, nz, ny, nx = _volume3(volume)
+    labels, info, counts = _label(vol, level, SIDES[side])
+    n_comp, n_points, largest, root = counts.tolist()
+    return labels, info, {"components": n_comp, "points": n_points, "largest": largest, "largest_root": root}
+
+
+@torch.no_grad()
+def filter_components(volume, level, min_points=0, keep_largest=0, protect_boundary=False, fill_cavities=False):
+    """volume [nz, ny, nx] without its small solids and / or its cavities: (filtered volume fp32, report).  The mesh of the result is
+    the mesh of `volume` without the dropped components' vertices and triangles; everything else keeps its bits and its order.
+    min_points: inside components with fewer lattice points are set to -inf.  keep_largest=k: so are those smaller than the k-th largest
+    (a torch.topk over the counts on the device; ties with the k-th are kept, so the result does not depend on an order).  Both may be
+    given: the larger threshold holds.  protect_boundary: components that touch the volume's boundary are never dropped.
+    fill_cavities: afterwards, every outside component of the result that does not touch the boundary is set to +inf -- inside first, then
+    cavities, so a floater inside a bubble goes with the bubble.
+    report: "threshold" (the min_points applied), "components_dropped", "points_dropped", "cavities_filled", "points_filled"."""
+    vol, nz, ny, nx = _volume3(volume)
+    min_points, keep_largest = int(min_points), int(keep_largest)
+    if min_points < 0 or keep_largest < 0:
+        raise ValueError(f"min_points={min_points}, keep_largest={keep_largest}: neither may be negative")
+    out = vol.clone() if vol.data_ptr() == volume.data_ptr() else vol
+    zero = torch.zeros(2, dtype=torch.int64, device=vol.device)
+    dropped, filled, threshold = zero, zero, min_points
+    if min_points > 0 or keep_largest > 0:
+        labels, info, _ = _label(out, level, 0)
+        if keep_largest > 0:
+            sizes = (info.reshape(-1) & COUNT_MASK)
+            kth = int(torch.topk(sizes, min(keep_largest, sizes.numel()), sorted=True).values[-1])
+            threshold = max(threshold, kth)
+        dropped = _filter(out, labels, info, 0, threshold, protect_boundary, out)
+    if fill_cavities:
+        labels, info, _ = _label(out, level, 1)
+        filled = _filter(out, labels, info, 1, ALL_POINTS, True, out)
+    d, f = dropped.tolist(), filled.tolist()
+    return out, {"threshold": threshold, "components_dropped": d[0], "points_dropped": d[1], "cavities_filled": f[0], "points_filled": f[1]}
+
+
+def vertex_components(keys, labels):
+    """The component of each mesh vertex: the label of the end of its edge that is on the labelled side.  keys: int64 [V] from
+    mesh_from_volume(return_keys=True) (lattice point * 8 + edge slot); labels: int32 [nz, ny, nx] of label_components on the same
+    volume and level.  Plain torch on the device; int32 [V]."""
+    nz, ny, nx = labels.shape
+    flat = labels.reshape(-1)
+    p, slot = keys >> 3, keys & 7
+    step = torch.tensor([dx + dy * nx + dz * nx * ny for dx, dy, dz in SLOT_OFFSETS] + [0], dtype=torch.int64, device=keys.device)
+    near, far = flat[p], flat[p + step[slot]]
+    return torch.where(near >= 0, near, far)
+
+
 def unit_normals(grad, axis_scale=None):
     """-grad / |grad| (grad first multiplied by axis_scale), 0 where the length is 0 or not finite: fp32, |g| = sqrt(gx gx + gy gy + gz gz)."""
     g = grad.float()
@@ -160,23 +266,38 @@ def vertex_albedo(field, vertices, chunk=1 << 20):
 
 @torch.no_grad()
 def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offset=None, scene_scale=None, normals=True, albedo=True,
-                 slab_points=1 << 22, chunk=1 << 20):
+                 slab_points=1 << 22, chunk=1 << 20, min_component_points=0, keep_largest=0, protect_boundary=False, fill_cavities=False,
+                 components=False):
     """Mesh of the level set `level` of the field's density on a resolution^3 lattice over `bounds` (scene coordinates: the normalised
     cube).  Returns a dict: "vertices" fp32 [V, 3] in scene coordinates; "faces" int32 [T, 3], normals out of the dense side; "level";
     "normals" fp32 [V, 3]: -grad sigma at the vertices (normals.density_gradient, times 1 / scene_scale when that is given: the metric
     east / north / up frame), unit length, 0 where the gradient is 0 or not finite; "albedo" fp32 [V, 3]; "vertices_utm" fp64 [V, 3] =
     vertices * scene_scale + scene_offset when both are given.
     level: a density.  The default, level_from_opacity(0.5, 2 / 128) -- half opacity over one step of a 128-sample render -- is a guess
-    until it has been measured on a converged scene."""
+    until it has been measured on a converged scene.
+    min_component_points, keep_largest, protect_boundary, fill_cavities: filter_components on the volume in front of the extraction;
+    the dict then also carries its "report".  All off by default (no component call is made, the result keeps today's bits): what a
+    good min_component_points is has not been measured.  components: also "component" int32 [V], the root id of each vertex' solid
+    (label_components of the volume that was meshed), and "component_points" int32 [V], that solid's lattice points."""
     from .normals import _axis_scale, density_gradient
     if level is None:
         level = level_from_opacity(0.5, 2.0 / 128)
     shape = (int(resolution),) * 3 if isinstance(resolution, int) else tuple(resolution)
     origin, spacing = lattice_of(shape, bounds)
     volume = density_volume(field, shape, bounds, slab_points=slab_points)
-    vertices, faces = mesh_from_volume(volume, level, origin, spacing)
+    cleanup = {}
+    if min_component_points or keep_largest or fill_cavities:
+        volume, cleanup["report"] = filter_components(volume, level, min_component_points, keep_largest, protect_boundary, fill_cavities)
+    if components:
+        vertices, faces, keys = mesh_from_volume(volume, level, origin, spacing, return_keys=True)
+        labels, info, _ = label_components(volume, level)
+        cleanup["component"] = vertex_components(keys, labels)
+        cleanup["component_points"] = info.reshape(-1)[cleanup["component"].long()] & COUNT_MASK
+        del keys, labels, info
+    else:
+        vertices, faces = mesh_from_volume(volume, level, origin, spacing)
     del volume
-    mesh = {"vertices": vertices, "faces": faces, "level": float(level)}
+    mesh = {"vertices": vertices, "faces": faces, "level": float(level), **cleanup}
     if normals:
         axis = _axis_scale(scene_scale)
         grads = [density_gradient(field, vertices[i:i + chunk])[1] for i in range(0, vertices.shape[0], chunk)]
@@ -198,7 +319,7 @@ def _host(a):
 def save_ply(path, mesh):
     """Binary little-endian PLY of a mesh dict: the vertices ("vertices_utm" where the dict has it, else "vertices") as float, or as
     double where they are fp64 (UTM metres do not fit a float); "normals" as nx ny nz (float) and "albedo" as uchar red green blue
-    (clipped to [0, 1], times 255, rounded) where present; "faces" as lists of three int32."""
+    (clipped to [0, 1], times 255, rounded) where present; "component" as int component; "faces" as lists of three int32."""
     xyz = _host(mesh["vertices_utm"] if mesh.get("vertices_utm") is not None else mesh["vertices"])
     faces = _host(mesh["faces"]).astype("<i4").reshape(-1, 3)
     double = xyz.dtype == np.float64
@@ -213,6 +334,9 @@ def save_ply(path, mesh):
     if mesh.get("albedo") is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
         header += [f"property uchar {a}" for a in ("red", "green", "blue")]
+    if mesh.get("component") is not None:
+        fields += [("component", "<i4")]
+        header += ["property int component"]
     header += [f"element face {faces.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     vert = np.zeros(n, dtype=fields)
     for c, a in enumerate("xyz"):
@@ -225,6 +349,8 @@ def save_ply(path, mesh):
         rgb = np.rint(np.clip(np.nan_to_num(_host(mesh["albedo"]).astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
         for c, a in enumerate(("red", "green", "blue")):
             vert[a] = rgb[:, c]
+    if mesh.get("component") is not None:
+        vert["component"] = _host(mesh["component"]).astype("<i4")
     face = np.zeros(faces.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
     face["n"] = 3
     face["v"] = faces

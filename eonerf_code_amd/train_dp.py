@@ -36,7 +36,10 @@ size reach that render as they reach the validation renders.  Without the flag n
 `--mesh_out PATH` writes, after the last step and on rank 0 only, a triangle mesh of the field's density level set as a binary PLY
 (eonerf_code_amd.mesh.extract_mesh / save_ply: marching tetrahedra on a `--mesh_res`^3 lattice over the normalised cube, per-vertex
 normals and albedo).  `--mesh_level` is the density of the level set; its default (half opacity over one render step of 128 samples) is
-a guess that has not been measured on a converged scene.  Without the flag nothing changes.
+a guess that has not been measured on a converged scene.  `--mesh_min_component N` drops every solid of fewer than N lattice points,
+`--mesh_keep_largest K` all but the K largest, `--mesh_fill_cavities` the closed inner surfaces no view can see
+(mesh.filter_components); all three are off by default -- a good N has not been measured -- and act only together with `--mesh_out`;
+with any of them the PLY also carries each vertex' component id.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -88,6 +91,9 @@ def main():
     ap.add_argument("--mesh_out", default=None, help="where rank 0 saves a PLY mesh of the density level set after the last step")
     ap.add_argument("--mesh_res", type=int, default=256, help="lattice points per axis of the mesh extraction")
     ap.add_argument("--mesh_level", type=float, default=None, help="density of the extracted level set (default: mesh.level_from_opacity(0.5, 2 / 128))")
+    ap.add_argument("--mesh_min_component", type=int, default=0, help="drop solids of fewer lattice points from the mesh (0: keep all; only with --mesh_out)")
+    ap.add_argument("--mesh_keep_largest", type=int, default=0, help="keep the K largest solids of the mesh, ties included (0: keep all; only with --mesh_out)")
+    ap.add_argument("--mesh_fill_cavities", action="store_true", help="drop closed inner surfaces from the mesh (only with --mesh_out)")
     ap.add_argument("--rpc_correction", action="store_true", help="learn a 3-D offset per image, added to that image's ray origins (opt.py:80); single process only")
     ap.add_argument("--rpc_lr", type=float, default=None, help="learning rate of the offsets (default: --lr)")
     ap.add_argument("--resume", default=None, help="checkpoint to continue from (weights, optimizer state and, with --rpc_correction, the offsets)")
@@ -234,11 +240,18 @@ def main():
                     print(f"step={step} | ortho={path} | cells={int((res['count'] > 0).sum())}/{oh * ow}", flush=True)
                 if args.mesh_out and rank == 0:
                     from .mesh import extract_mesh, save_ply
-                    mesh = extract_mesh(field, resolution=args.mesh_res, level=args.mesh_level)
+                    cleaned = bool(args.mesh_min_component or args.mesh_keep_largest or args.mesh_fill_cavities)
+                    mesh = extract_mesh(field, resolution=args.mesh_res, level=args.mesh_level, min_component_points=args.mesh_min_component,
+                                        keep_largest=args.mesh_keep_largest, fill_cavities=args.mesh_fill_cavities, components=cleaned)
                     os.makedirs(os.path.dirname(os.path.abspath(args.mesh_out)), exist_ok=True)
                     save_ply(args.mesh_out, mesh)
                     print(f"step={step} | mesh={args.mesh_out} | vertices={mesh['vertices'].shape[0]} | faces={mesh['faces'].shape[0]} | "
                           f"level={mesh['level']:.6g}", flush=True)
+                    if cleaned:
+                        sizes = mesh["component_points"]
+                        print(f"step={step} | mesh_components={int(torch.unique(mesh['component']).numel())} | "
+                              f"smallest_component={int(sizes.min()) if sizes.numel() else 0} | " +
+                              " | ".join(f"{k}={v}" for k, v in mesh["report"].items()), flush=True)
                 if args.dump_params:                                        # replica-equality checks of the tests
                     torch.save(field.flat_params().detach().cpu(), f"{args.dump_params}.rank{rank}")
                 if torch.distributed.is_initialized():

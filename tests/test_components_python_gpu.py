@@ -1,0 +1,228 @@
+"""GPU: mesh clean-up through the Python layer (eonerf_code_amd/mesh.py).  The rule is pinned at the C ABI
+(tests/test_components_gpu.py); here, on a 33^3 scene of two spheres, a 3-point speck and a hollow sphere: what filter_components drops
+and reports, that the mesh of its result is the sub-mesh, vertex_components, the PLY column, that extract_mesh with default arguments
+keeps its bits and makes no component call, and the launcher's flags."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import components_restated as cr
+import mesh_restated as mr
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N = 33
+SPECK = [(20, 25, 5), (20, 25, 6), (20, 25, 7)]          # (k, j, i)
+
+
+def scene(floater_in_the_bubble=False):
+    z, y, x = np.meshgrid(np.arange(N), np.arange(N), np.arange(N), indexing="ij")
+    dist = lambda c: np.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2)      # noqa: E731
+    hollow = dist((21.9, 22.1, 22.2))
+    f = np.maximum(np.maximum(5.3 - dist((8.1, 8.2, 7.9)), 3.4 - dist((24.2, 7.1, 8.3))), np.minimum(8.3 - hollow, hollow - 4.2)).astype(np.float32)
+    for k, j, i in SPECK:
+        f[k, j, i] = 1.0
+    if floater_in_the_bubble:
+        f[22, 22, 22] = 1.0
+    return f
+
+
+@pytest.fixture(scope="module")
+def restated():
+    f = scene()
+    f.setflags(write=False)
+    inside, outside = cr.label(f, 0.0, 0), cr.label(f, 0.0, 1)
+    sizes = sorted((inside["info"].reshape(-1)[np.nonzero(inside["info"].reshape(-1))[0]] & 0x7FFFFFFF).tolist())
+    assert inside["counts"][0] == 4 and sizes[0] == 3 and sizes[1] > 100 and sizes[2] > 2 * sizes[1] and sizes[3] > 2 * sizes[2], sizes
+    assert outside["counts"][0] == 2 and not (inside["info"] & cr.BOUNDARY).any()
+    return {"f": f, "inside": inside, "outside": outside, "sizes": sizes, "mesh": mr.extract(f, 0.0)}
+
+
+def device(f):
+    return torch.from_numpy(np.array(f)).cuda()
+
+
+def mesh_of(vol):
+    from eonerf_code_amd.mesh import mesh_from_volume
+    v, t, k = mesh_from_volume(vol, 0.0, return_keys=True)
+    return v.cpu().numpy(), t.cpu().numpy(), k.cpu().numpy()
+
+
+def assert_sub_mesh(restated, vol, dropped_roots, labels):
+    """The device mesh of `vol` is restated["mesh"] without the vertices whose component (by `labels`) is in dropped_roots."""
+    mesh = restated["mesh"]
+    comp = cr.vertex_components(mesh["keys"], labels, (N, N, N))
+    keep = ~np.isin(comp, dropped_roots)
+    new_id = np.cumsum(keep) - 1
+    tri_keep = keep[mesh["triangles"]].all(axis=1)
+    v, t, k = mesh_of(vol)
+    assert 0 < keep.sum() < len(keep)
+    assert np.array_equal(k, mesh["keys"][keep]) and v.tobytes() == mesh["vertices"][keep].tobytes()
+    assert np.array_equal(mr.rotate_smallest_first(t), mr.rotate_smallest_first(new_id[mesh["triangles"][tri_keep]].astype(np.int32)))
+    return v, t
+
+
+def test_label_components_and_vertex_components_agree_with_the_restatement(restated):
+    from eonerf_code_amd.mesh import label_components, mesh_from_volume, vertex_components
+    vol = device(restated["f"])
+    for side, name in ((0, "inside"), (1, "outside")):
+        labels, info, counts = label_components(vol, 0.0, side=name)
+        want = restated[name]
+        assert labels.dtype == torch.int32 and labels.shape == (N, N, N) and info.shape == (N, N, N)
+        assert labels.cpu().numpy().tobytes() == want["labels"].tobytes() and info.cpu().numpy().tobytes() == want["info"].tobytes()
+        assert (counts["components"], counts["points"], counts["largest"], counts["largest_root"]) == want["counts"]
+        v, t, keys = mesh_from_volume(vol, 0.0, return_keys=True)
+        comp = vertex_components(keys, labels)
+        assert comp.dtype == torch.int32 and np.array_equal(comp.cpu().numpy(), cr.vertex_components(restated["mesh"]["keys"], want["labels"], (N, N, N)))
+        per_triangle = comp[t.long()]
+        assert bool((per_triangle == per_triangle[:, :1]).all()) and len(torch.unique(comp)) == (4 if side == 0 else 2)
+    with pytest.raises(ValueError):
+        label_components(vol, 0.0, side="both")
+    with pytest.raises(ValueError):
+        label_components(vol.cpu(), 0.0)
+
+
+def test_min_points_drops_only_the_speck(restated):
+    from eonerf_code_amd.mesh import filter_components
+    vol = device(restated["f"])
+    before = vol.clone()
+    out, report = filter_components(vol, 0.0, min_points=4)
+    assert report == {"threshold": 4, "components_dropped": 1, "points_dropped": 3, "cavities_filled": 0, "points_filled": 0}
+    assert torch.equal(vol.view(torch.int32), before.view(torch.int32)) and out.data_ptr() != vol.data_ptr()
+    want, _ = cr.filter_volume(restated["f"], restated["inside"]["labels"], restated["inside"]["info"], 0, 4, False)
+    assert out.cpu().numpy().tobytes() == want.tobytes()
+    changed = np.nonzero(out.cpu().numpy() != restated["f"])
+    assert sorted(zip(*(c.tolist() for c in changed))) == SPECK
+    speck_root = (SPECK[0][0] * N + SPECK[0][1]) * N + SPECK[0][2]
+    assert_sub_mesh(restated, out, [speck_root], restated["inside"]["labels"])
+    same, report = filter_components(vol, 0.0)
+    assert torch.equal(same.view(torch.int32), before.view(torch.int32)) and report["components_dropped"] == 0 and report["threshold"] == 0
+
+
+def test_keep_largest_leaves_the_bigger_solids(restated):
+    from eonerf_code_amd.mesh import filter_components, label_components
+    vol = device(restated["f"])
+    sizes = restated["sizes"]
+    info = restated["inside"]["info"].reshape(-1)
+    for k, n_drop in ((1, 3), (2, 2), (3, 1), (4, 0), (9, 0)):
+        out, report = filter_components(vol, 0.0, keep_largest=k)
+        assert report["components_dropped"] == n_drop and report["points_dropped"] == sum(sizes[:n_drop]), (k, report)
+        assert report["threshold"] == (sizes[4 - k] if k <= 4 else 0)
+        _, _, counts = label_components(out, 0.0)
+        assert counts["components"] == 4 - n_drop and counts["largest"] == sizes[-1]
+    out, report = filter_components(vol, 0.0, keep_largest=1)
+    roots = [int(r) for r in np.nonzero(info)[0] if (info[r] & 0x7FFFFFFF) < sizes[-1]]
+    assert_sub_mesh(restated, out, roots, restated["inside"]["labels"])
+    out, report = filter_components(vol, 0.0, min_points=sizes[1] + 1, keep_largest=4)          # the larger threshold holds
+    assert report["threshold"] == sizes[1] + 1 and report["components_dropped"] == 2
+    with pytest.raises(ValueError):
+        filter_components(vol, 0.0, min_points=-1)
+
+
+def test_fill_cavities_drops_the_inner_surface_and_leaves_a_closed_oriented_mesh(restated):
+    from eonerf_code_amd.mesh import filter_components
+    vol = device(restated["f"])
+    outside = restated["outside"]
+    flat = outside["info"].reshape(-1)
+    cavity = [int(r) for r in np.nonzero(flat)[0] if not flat[r] & cr.BOUNDARY]
+    assert len(cavity) == 1
+    out, report = filter_components(vol, 0.0, fill_cavities=True)
+    assert report == {"threshold": 0, "components_dropped": 0, "points_dropped": 0, "cavities_filled": 1, "points_filled": int(flat[cavity[0]] & 0x7FFFFFFF)}
+    want, _ = cr.filter_volume(restated["f"], outside["labels"], outside["info"], 1, 1 << 29, True)
+    assert out.cpu().numpy().tobytes() == want.tobytes()
+    v, t = assert_sub_mesh(restated, out, cavity, outside["labels"])
+    most, unpaired = mr.edge_report(t)
+    assert most == 1 and len(unpaired) == 0                                   # every edge twice, once per direction
+    assert mr.euler_characteristic(len(v), t) == 2 * 4 and len(t) < len(restated["mesh"]["triangles"])
+    # everything at once; and a floater inside the bubble goes with the bubble, though min_points alone would have kept the surface around it
+    out, report = filter_components(vol, 0.0, min_points=4, fill_cavities=True)
+    assert (report["components_dropped"], report["points_dropped"], report["cavities_filled"]) == (1, 3, 1)
+    bubble = device(scene(floater_in_the_bubble=True))
+    out, report = filter_components(bubble, 0.0, fill_cavities=True)
+    assert report["cavities_filled"] == 1 and report["points_filled"] == int(flat[cavity[0]] & 0x7FFFFFFF) - 1
+    v2, t2, _ = mesh_of(out)
+    assert v2.tobytes() == v.tobytes() and np.array_equal(t2, t)
+
+
+def test_ply_component_column_round_trips(restated, tmp_path):
+    from eonerf_code_amd.mesh import label_components, mesh_from_volume, save_ply, vertex_components
+    vol = device(restated["f"])
+    v, t, keys = mesh_from_volume(vol, 0.0, return_keys=True)
+    comp = vertex_components(keys, label_components(vol, 0.0)[0])
+    path = str(tmp_path / "c.ply")
+    save_ply(path, {"vertices": v, "faces": t, "component": comp})
+    header = open(path, "rb").read().split(b"end_header\n")[0].decode("ascii").split("\n")
+    assert "property int component" in header and header.index("property int component") < header.index(f"element face {t.shape[0]}")
+    got = mr.read_ply(path)
+    assert got["component"].dtype == np.int32 and np.array_equal(got["component"], comp.cpu().numpy())
+    assert np.array_equal(got["faces"], t.cpu().numpy()) and np.array_equal(got["x"], v[:, 0].cpu().numpy())
+    save_ply(path, {"vertices": v, "faces": t})
+    assert "component" not in mr.read_ply(path)
+
+
+def test_extract_mesh_defaults_keep_their_bits_and_make_no_component_call(monkeypatch):
+    import test_march_python_gpu as tmp_
+    from eonerf_code_amd import _lib
+    from eonerf_code_amd.mesh import density_volume, extract_mesh, filter_components, mesh_from_volume
+    f = tmp_._field("fp32")
+    n, bounds = 17, ((-1.0, -0.9, -0.8), (1.0, 0.7, 0.9))
+    vol = density_volume(f, n, bounds)
+    for q in (0.5, 0.7, 0.8, 0.9, 0.95, 0.98):            # the first level at which the seeded field has more than one solid
+        level = float(torch.quantile(vol.reshape(-1), q))
+        lab = cr.label(vol.cpu().numpy(), level, 0)
+        if lab["counts"][0] >= 2:
+            break
+    assert lab["counts"][0] >= 2 and lab["counts"][2] < lab["counts"][1]
+    calls = []
+    L = _lib.lib()
+    for name in _lib.CC_SYMBOLS:
+        monkeypatch.setattr(L, name, (lambda name: lambda *a: calls.append(name))(name))
+    plain = extract_mesh(f, resolution=n, level=level, bounds=bounds)
+    explicit = extract_mesh(f, resolution=n, level=level, bounds=bounds, min_component_points=0, keep_largest=0, protect_boundary=False,
+                            fill_cavities=False, components=False)
+    assert calls == [] and list(plain) == list(explicit) == ["vertices", "faces", "level", "normals", "albedo"]
+    for key in plain:
+        assert plain[key] == explicit[key] if key == "level" else torch.equal(plain[key], explicit[key]), key
+    monkeypatch.undo()
+    mesh = extract_mesh(f, resolution=n, level=level, bounds=bounds, components=True, normals=False, albedo=False)
+    assert torch.equal(mesh["vertices"], plain["vertices"]) and torch.equal(mesh["faces"], plain["faces"]) and "report" not in mesh
+    ref = mr.extract(vol.cpu().numpy(), level)
+    want = cr.vertex_components(ref["keys"], lab["labels"], (n, n, n))
+    assert mesh["component"].dtype == torch.int32 and np.array_equal(mesh["component"].cpu().numpy(), want)
+    assert np.array_equal(mesh["component_points"].cpu().numpy(), (lab["info"].reshape(-1)[want] & 0x7FFFFFFF).astype(np.int32))
+    threshold = lab["counts"][2]
+    cleaned = extract_mesh(f, resolution=n, level=level, bounds=bounds, min_component_points=threshold, components=True, normals=False, albedo=False)
+    from eonerf_code_amd.mesh import lattice_of
+    origin, spacing = lattice_of(n, bounds)
+    v, t = mesh_from_volume(filter_components(vol, level, min_points=threshold)[0], level, origin, spacing)
+    assert torch.equal(cleaned["vertices"], v) and torch.equal(cleaned["faces"], t) and 0 < v.shape[0] < plain["vertices"].shape[0]
+    assert cleaned["report"]["components_dropped"] == lab["counts"][0] - int((lab["info"].reshape(-1) & 0x7FFFFFFF == threshold).sum())
+    assert int(cleaned["component_points"].min()) >= threshold
+
+
+def test_launcher_flags_write_a_mesh_with_no_small_component(tmp_path):
+    ply = str(tmp_path / "out" / "scene.ply")
+    # the smallest run of tests/test_train_dp_mesh_gpu.py: 16 steps, a 17^3 lattice, a level inside the young field's density range
+    cmd = [sys.executable, "-m", "eonerf_code_amd.train_dp", "--synthetic_rays", "2048", "--batch_size", "512", "--n_images", "2",
+           "--n_samples", "64", "--max_train_steps", "16", "--check_every", "8", "--logs_dir", str(tmp_path / "logs"), "--exp_name", "t",
+           "--mesh_out", ply, "--mesh_res", "17", "--mesh_level", "0.3", "--mesh_min_component", "5", "--mesh_keep_largest", "3", "--mesh_fill_cavities"]
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), EONERF_DETERMINISTIC="1")
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    m = re.search(r"mesh_components=(\d+) \| smallest_component=(\d+) \| threshold=(\d+) \| components_dropped=(\d+) \| points_dropped=(\d+) \| "
+                  r"cavities_filled=(\d+) \| points_filled=(\d+)", r.stdout)
+    assert m and os.path.exists(ply), r.stdout[-2000:]
+    print(m.group(0))
+    n_comp, smallest, threshold = int(m.group(1)), int(m.group(2)), int(m.group(3))
+    assert threshold >= 5 and smallest >= threshold and 1 <= n_comp
+    got = mr.read_ply(ply)
+    assert "component" in got and len(np.unique(got["component"])) == n_comp and len(got["faces"]) > 0
+    per_triangle = got["component"][got["faces"]]
+    assert (per_triangle == per_triangle[:, :1]).all()
+    most, _ = mr.edge_report(got["faces"])
+    assert most == 1
