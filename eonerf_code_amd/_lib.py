@@ -53,6 +53,8 @@ NORMALS_SYMBOLS = ["eonerf_normals_version", "eonerf_density_grad_workspace_byte
 MESH_SYMBOLS = ["eonerf_mesh_version", "eonerf_mesh_lattice_points", "eonerf_mesh_workspace_bytes", "eonerf_mesh_count", "eonerf_mesh_emit"]
 # include/eonerf_components.h: connected components of a volume under the mesher's connectivity, and the floater / cavity filter (mesh.py)
 CC_SYMBOLS = ["eonerf_cc_version", "eonerf_cc_workspace_bytes", "eonerf_cc_label", "eonerf_cc_filter"]
+# include/eonerf_layout.h: the read-only workspace layout query (tests decode the saved slabs through it)
+LAYOUT_SYMBOLS = ["eonerf_layout_version", "eonerf_workspace_layout"]
 
 
 class EonerfRpc(C.Structure):
@@ -85,6 +87,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_normals.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_mesh.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_components.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_layout.h"))
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -245,8 +248,10 @@ def lib():
     L.eonerf_cc_workspace_bytes.argtypes = [i, i, i]
     L.eonerf_cc_label.argtypes = [vp, i, i, i, fp, i, vp, vp, vp, vp, sz, vp]
     L.eonerf_cc_filter.argtypes = [vp, vp, vp, i, i, i, i, C.c_int64, i, vp, vp, vp]
+    L.eonerf_layout_version.restype = i
+    L.eonerf_workspace_layout.argtypes = [vp, i, i, i, C.POINTER(C.c_uint64), i]
     for name in (SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS + QUANTILE_SYMBOLS
-                 + ORTHO_SYMBOLS + POSE_SYMBOLS + NORMALS_SYMBOLS + MESH_SYMBOLS + CC_SYMBOLS):
+                 + ORTHO_SYMBOLS + POSE_SYMBOLS + NORMALS_SYMBOLS + MESH_SYMBOLS + CC_SYMBOLS + LAYOUT_SYMBOLS):
         getattr(L, name)
     _lib = L
     return L

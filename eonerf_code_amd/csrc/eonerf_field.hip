@@ -5,6 +5,7 @@
 #include "eonerf_ctx.h"
 #include "eonerf_raygen.h"
 #include "eonerf_rpc_dev.h"
+#include "eonerf_layout_table.h"
 
 extern "C" {
 
@@ -143,6 +144,14 @@ int eonerf_generate_rays(const eonerf_rpc* rpc, const double* cols, const double
     for (int k = 0; k < 3; ++k) { a.offset[k] = offset ? offset[k] : 0.f; a.scale[k] = scale ? scale[k] : 1.f; }
     a.raw8 = raw8; a.rays = rays; a.geo = geo;
     return (int)eo_launch_raygen(a, (hipStream_t)stream);
+}
+
+// ---- include/eonerf_layout.h: where the next call of that kind on this context puts its buffers (host arithmetic only) ----
+int eonerf_layout_version(void) { return EONERF_LAYOUT_VERSION; }
+
+int eonerf_workspace_layout(const eonerf_ctx* ctx, int kind, int n, int flags, uint64_t* out, int cap) {
+    if (!ctx) return EONERF_E_ARG;
+    return workspace_layout_table(carve_cfg(ctx), kind, n, flags, out, cap);
 }
 
 }  // extern "C"

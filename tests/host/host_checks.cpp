@@ -9,6 +9,8 @@
 //   * eonerf_wgrad_plan.h: the job table and slice plan of the weight-gradient GEMM launch for every reachable combination of precision,
 //     backward path, pass set and switches -- the table fits, the items are a running sum that fits deterministic mode's partial buffer,
 //     every operand stays inside the slab block it starts in, the wave grid covers the product, the riders sit on the right job.
+//   * eonerf_layout_table.h (include/eonerf_layout.h): over the same enumeration of layouts, every offset eonerf_workspace_layout reports
+//     is the carve's own pointer minus the base, a buffer the carve does not have is UINT64_MAX, and the refusals write nothing.
 // No HIP runtime call is made (GPU sanitizers are not available on this pool; the device side is covered by the parity tests).
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,6 +21,7 @@
 #include "../../eonerf_code_amd/csrc/eonerf_pack.h"
 #include "../../eonerf_code_amd/csrc/eonerf_carve.h"
 #include "../../eonerf_code_amd/csrc/eonerf_wgrad_plan.h"
+#include "../../eonerf_code_amd/csrc/eonerf_layout_table.h"
 
 static int g_fail = 0;
 #define CHECK(c, ...) do { if (!(c)) { ++g_fail; fprintf(stderr, "FAIL %s:%d: %s -- ", __FILE__, __LINE__, #c); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } } while (0)
@@ -140,6 +143,18 @@ static void check_spans(std::vector<Span>& v, size_t bytes) {
     }
 }
 
+// include/eonerf_layout.h: entry k of the table against the carve's own pointer (null: the layout has no such buffer)
+static void check_layout_pass(const char* what, const uint64_t* t, const PassBuffers& b, const uint8_t* base) {
+    const void* m[EONERF_PASS_MEMBERS] = {b.counts, b.offsets, b.n_pts, b.px, b.py, b.pz, b.tmid, b.delta, b.sigma, b.albedo, b.ts, b.tb, b.simg,
+                                          b.act, b.grd, b.masks, b.g_sigma, b.g_albedo, b.g_ts, b.g_tb, b.g_emb, b.g_pos};
+    static_assert(EONERF_PASS_G_POS == 21 && EONERF_PASS_ACT == 13 && EONERF_PASS_SIMG == 12, "documented order of the pass members");
+    for (int k = 0; k < EONERF_PASS_MEMBERS; ++k) {
+        const uint64_t want = m[k] ? (uint64_t)(reinterpret_cast<const uint8_t*>(m[k]) - base) : UINT64_MAX;
+        CHECK(t[k] == want, "%s member %d: layout query %llu, carve %llu", what, k, (unsigned long long)t[k], (unsigned long long)want);
+    }
+}
+static uint64_t off_or_none(const void* p, const uint8_t* base) { return p ? (uint64_t)(reinterpret_cast<const uint8_t*>(p) - base) : UINT64_MAX; }
+
 static void check_carve(const CarveCfg& cfg, int n_rays, int flags) {
     const RenderWs m = carve_render(cfg, nullptr, n_rays, flags);                 // measuring pass
     // a fake, never dereferenced base: only differences of pointers are formed
@@ -178,6 +193,18 @@ static void check_carve(const CarveCfg& cfg, int n_rays, int flags) {
     CHECK((w.cam.g_pos != nullptr) == (train && od), "input-gradient buffer of a density-only training pass");
     CHECK((w.sun.px != nullptr) == ((flags & EONERF_F_SHADOWS) && !od), "sun pass buffers");
     CHECK((w.enc_part != nullptr) == (train && (flags & EONERF_F_SHADOWS) && !od && cfg.pipe && cfg.enc_part_wgs > 0), "encoding partials");
+    // the layout query reports exactly this carve
+    uint64_t t[EONERF_LAYOUT_ENTRIES + 1];
+    t[EONERF_LAYOUT_ENTRIES] = 0x5a5a5a5a5a5a5a5aull;
+    CHECK(workspace_layout_table(cfg, EONERF_LAYOUT_RENDER, n_rays, flags, t, EONERF_LAYOUT_ENTRIES) == EONERF_LAYOUT_ENTRIES, "layout query refused");
+    CHECK(t[EONERF_LAYOUT_ENTRIES] == 0x5a5a5a5a5a5a5a5aull, "layout query wrote beyond its table");
+    CHECK(t[EONERF_LAYOUT_P_CAP] == p_cap && t[EONERF_LAYOUT_BYTES] == w.bytes, "layout query: p_cap %llu bytes %llu", (unsigned long long)t[0], (unsigned long long)t[1]);
+    CHECK(t[EONERF_LAYOUT_M_BOTT] == off_or_none(w.m_bott, base) && t[EONERF_LAYOUT_DY_IN] == off_or_none(w.pipe.dy_in, base) &&
+          t[EONERF_LAYOUT_ENC_PART] == off_or_none(w.enc_part, base), "layout query: m_bott / dy_in / enc_part");
+    check_layout_pass("render cam", t + EONERF_LAYOUT_CAM, w.cam, base);
+    check_layout_pass("render sun", t + EONERF_LAYOUT_SUN, w.sun, base);
+    for (int k = 0; k < EONERF_LAYOUT_ENTRIES; ++k)
+        if (k != EONERF_LAYOUT_P_CAP && k != EONERF_LAYOUT_BYTES && t[k] != UINT64_MAX) CHECK(t[k] % 256 == 0 && t[k] < w.bytes, "layout entry %d = %llu", k, (unsigned long long)t[k]);
 }
 
 // eonerf_field_forward / eonerf_query_density (carve_field) and eonerf_field_forward_train / eonerf_field_backward (carve_field_train)
@@ -206,6 +233,12 @@ static void check_carve_field(const CarveCfg& cfg, int n) {
         CHECK(w.b.act && w.b.grd && w.b.masks && w.b.g_sigma && w.b.g_pos && w.m_bott && w.queue, "field training buffers");
         CHECK((w.b.albedo != nullptr) == full && (w.b.g_albedo != nullptr) == full && (w.b.g_emb != nullptr) == full, "field head buffers");
         CHECK(w.bytes > carve_field(cfg, nullptr, (int)p_cap).bytes || !full, "a training layout holds the inference layout and more");
+        uint64_t t[EONERF_LAYOUT_ENTRIES];
+        CHECK(workspace_layout_table(cfg, EONERF_LAYOUT_FIELD_TRAIN, n, density_only, t, EONERF_LAYOUT_ENTRIES) == EONERF_LAYOUT_ENTRIES, "field layout query refused");
+        CHECK(t[EONERF_LAYOUT_P_CAP] == p_cap && t[EONERF_LAYOUT_BYTES] == w.bytes && t[EONERF_LAYOUT_M_BOTT] == off_or_none(w.m_bott, base), "field layout query: p_cap / bytes / m_bott");
+        CHECK(t[EONERF_LAYOUT_DY_IN] == UINT64_MAX && t[EONERF_LAYOUT_ENC_PART] == UINT64_MAX, "field layout query: buffers of the render path");
+        check_layout_pass("field train", t + EONERF_LAYOUT_CAM, w.b, base);
+        for (int k = 0; k < EONERF_PASS_MEMBERS; ++k) CHECK(t[EONERF_LAYOUT_SUN + k] == UINT64_MAX, "field layout query: sun pass member %d", k);
     }
 }
 
@@ -341,6 +374,13 @@ int main() {
         for (int n : {0, 1, 255, 256, 257, 1000, 2097152}) check_carve_field(c, n);
     CHECK(slab_blocks_addressable(true, (size_t)p_cap_of(66050, 128)) && !slab_blocks_addressable(true, (size_t)p_cap_of(66051, 128)), "bf16 size guard");
     CHECK(slab_blocks_addressable(false, (size_t)p_cap_of(33024, 128)) && !slab_blocks_addressable(false, (size_t)p_cap_of(33025, 128)), "fp32 size guard");
+    {   // the layout query's refusals leave the table alone
+        uint64_t t[EONERF_LAYOUT_ENTRIES] = {7};
+        CHECK(workspace_layout_table(cfgs[1], EONERF_LAYOUT_RENDER, 37, EONERF_F_TRAIN, t, EONERF_LAYOUT_ENTRIES - 1) == EONERF_E_ARG && t[0] == 7, "short table");
+        CHECK(workspace_layout_table(cfgs[1], 2, 37, 0, t, EONERF_LAYOUT_ENTRIES) == EONERF_E_ARG && t[0] == 7, "unknown kind");
+        CHECK(workspace_layout_table(cfgs[1], EONERF_LAYOUT_FIELD_TRAIN, -1, 0, t, EONERF_LAYOUT_ENTRIES) == EONERF_E_ARG && t[0] == 7, "negative n");
+        CHECK(workspace_layout_table(cfgs[1], EONERF_LAYOUT_RENDER, 37, 0, nullptr, EONERF_LAYOUT_ENTRIES) == EONERF_E_ARG, "null table");
+    }
     check_wgrad_plans();
     if (g_fail) { fprintf(stderr, "%d check(s) failed\n", g_fail); return 1; }
     printf("host checks ok\n");
