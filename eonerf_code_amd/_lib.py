@@ -53,6 +53,8 @@ NORMALS_SYMBOLS = ["eonerf_normals_version", "eonerf_density_grad_workspace_byte
 MESH_SYMBOLS = ["eonerf_mesh_version", "eonerf_mesh_lattice_points", "eonerf_mesh_workspace_bytes", "eonerf_mesh_count", "eonerf_mesh_emit"]
 # include/eonerf_components.h: connected components of a volume under the mesher's connectivity, and the floater / cavity filter (mesh.py)
 CC_SYMBOLS = ["eonerf_cc_version", "eonerf_cc_workspace_bytes", "eonerf_cc_label", "eonerf_cc_filter"]
+# include/eonerf_mesh_dsm.h: a mesh rasterised from above into a DSM, a face raster and attribute rasters (mesh.rasterize_mesh)
+MESH_DSM_SYMBOLS = ["eonerf_mesh_dsm_version", "eonerf_mesh_dsm_rasterize", "eonerf_mesh_dsm_attributes"]
 # include/eonerf_layout.h: the read-only workspace layout query (tests decode the saved slabs through it)
 LAYOUT_SYMBOLS = ["eonerf_layout_version", "eonerf_workspace_layout"]
 
@@ -87,6 +89,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_normals.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_mesh.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_components.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_mesh_dsm.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eonerf_layout.h"))
     h = hashlib.sha1()
     for f in srcs:
@@ -248,10 +251,13 @@ def lib():
     L.eonerf_cc_workspace_bytes.argtypes = [i, i, i]
     L.eonerf_cc_label.argtypes = [vp, i, i, i, fp, i, vp, vp, vp, vp, sz, vp]
     L.eonerf_cc_filter.argtypes = [vp, vp, vp, i, i, i, i, C.c_int64, i, vp, vp, vp]
+    L.eonerf_mesh_dsm_version.restype = i
+    L.eonerf_mesh_dsm_rasterize.argtypes = [vp, C.c_int64, vp, C.c_int64, d3, d3, C.c_double, C.c_double, i, i, C.c_double, vp, vp, vp, vp, vp]
+    L.eonerf_mesh_dsm_attributes.argtypes = [vp, C.c_int64, vp, C.c_int64, d3, d3, C.c_double, C.c_double, i, i, C.c_double, vp, vp, i, vp, vp]
     L.eonerf_layout_version.restype = i
     L.eonerf_workspace_layout.argtypes = [vp, i, i, i, C.POINTER(C.c_uint64), i]
     for name in (SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS + QUANTILE_SYMBOLS
-                 + ORTHO_SYMBOLS + POSE_SYMBOLS + NORMALS_SYMBOLS + MESH_SYMBOLS + CC_SYMBOLS + LAYOUT_SYMBOLS):
+                 + ORTHO_SYMBOLS + POSE_SYMBOLS + NORMALS_SYMBOLS + MESH_SYMBOLS + CC_SYMBOLS + MESH_DSM_SYMBOLS + LAYOUT_SYMBOLS):
         getattr(L, name)
     _lib = L
     return L

@@ -12,6 +12,11 @@ the cavities; filter_components drops solids below a point count or all but the 
 the mesh of the filtered volume is the mesh of the original one without those components, bit for bit; vertex_components gives every
 vertex the id of its solid.  Every filter is off by default: what a good min_points is on a converged scene has not been measured.
 
+rasterize_mesh (include/eonerf_mesh_dsm.h) looks straight down on a mesh: for every cell of a georeferenced grid the altitude of the highest
+surface under the cell's centre, the face that gave it and per-vertex attributes interpolated there (an ortho view of albedo, normals or
+component ids).  evaluate_mesh_dsm sends that raster through dsm.mask_water -> register_dsm -> dsm_mae, which puts a mesh -- and with it the
+level and every clean-up filter -- on the scale of the validation DSM MAE.
+
 Not here: marching cubes, vertex refinement along the gradient, filters on area or height above ground, labelling of the mesh graph
 itself, simplification and welding, textures, skipping empty space through the occupancy grid while the volume is filled, volumes larger
 than one call, OBJ / glTF writers.
@@ -310,6 +315,95 @@ def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offs
         offset = torch.as_tensor(scene_offset, dtype=torch.float64).reshape(3).to(vertices.device)
         mesh["vertices_utm"] = vertices.double() * scale + offset
     return mesh
+
+
+def _mesh_arrays(mesh):
+    """(vertices fp32 [V, 3], faces int32 [T, 3]) in scene coordinates, contiguous, from a mesh dict or a pair."""
+    vertices, faces = (mesh["vertices"], mesh["faces"]) if isinstance(mesh, dict) else mesh
+    if vertices.device.type != "cuda" or faces.device != vertices.device:
+        raise ValueError("the mesh must be on the GPU (the rasteriser has no host form)")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("vertices [V, 3] and faces [T, 3]")
+    return vertices.detach().float().contiguous(), faces.detach().to(torch.int32).contiguous()
+
+
+@torch.no_grad()
+def rasterize_mesh(mesh, scene_offset, scene_scale, roi=None, grid=None, attributes=None, return_face=False, return_counts=False):
+    """The mesh seen straight from above by the rule of include/eonerf_mesh_dsm.h: fp32 [ysize, xsize], per cell the altitude of the
+    highest surface under the cell's centre, NaN where there is none.  Vertices go to UTM as pos = v * scene_scale + scene_offset in fp64
+    (the dataset's fp32 values, as dsm.rasterize_dsm takes them); the result does not depend on the order of the faces.
+    mesh: a dict of extract_mesh (its "vertices" and "faces"), or a (vertices, faces) pair in scene coordinates, on the GPU.
+    roi / grid: as in dsm.rasterize_dsm -- the ROI quadruple (x, y, size, res) of a lidar DSM, or (xoff, yoff, xsize, ysize, res) with
+    (xoff, yoff) the upper-left corner.  One of the two is required.
+    attributes: a dict of per-vertex fp32 tensors [V] or [V, C <= 8] (mesh["albedo"], mesh["normals"], ...), interpolated at the cell
+    centres on the winning face: rasters [ysize, xsize, C], NaN where the DSM is.
+    With none of attributes, return_face, return_counts the raster itself is returned; otherwise a dict: "dsm"; "attributes" (a dict
+    under the names given); "face" int32 [ysize, xsize], rows of `faces`, -1 where empty; "counts" = {"rasterised", "dropped",
+    "degenerate", "covered"} as ints.  Nothing is read back unless return_counts asks for it."""
+    from .dsm import _d3, grid_from_roi
+    vertices, faces = _mesh_arrays(mesh)
+    if grid is None and roi is not None:
+        grid = grid_from_roi(roi)
+    if grid is None:
+        raise ValueError("rasterize_mesh needs roi= or grid=")
+    xoff, yoff, xsize, ysize, res = float(grid[0]), float(grid[1]), int(grid[2]), int(grid[3]), float(grid[4])
+    dev = vertices.device
+    n_v, n_t = vertices.shape[0], faces.shape[0]
+    if n_v == 0:
+        vertices = torch.zeros(1, 3, dtype=torch.float32, device=dev)          # the library takes no null pointer
+    if n_t == 0:
+        faces = torch.zeros(1, 3, dtype=torch.int32, device=dev)
+    scale, offset = _d3(scene_scale), _d3(scene_offset)
+    cells = max(xsize, 0) * max(ysize, 0)
+    keys = torch.empty(max(cells, 1), dtype=torch.int64, device=dev)
+    dsm = torch.empty(max(ysize, 0), max(xsize, 0), dtype=torch.float32, device=dev)
+    want_face = return_face or bool(attributes)
+    face = torch.empty(max(ysize, 0), max(xsize, 0), dtype=torch.int32, device=dev) if want_face else None
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    tables = {}
+    for name, attr in (attributes or {}).items():
+        a = attr.detach().to(dev, torch.float32)
+        a = a.reshape(a.shape[0], -1).contiguous() if a.dim() else a.reshape(1, 1)
+        if a.shape[0] != n_v or not 1 <= a.shape[1] <= 8:
+            raise ValueError(f"attributes[{name!r}]: a per-vertex tensor [V] or [V, C <= 8] with V = {n_v}, not {tuple(attr.shape)}")
+        tables[name] = a if n_v else torch.zeros(1, a.shape[1], dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    rasters = {}
+    with torch.cuda.device(dev):
+        _lib.check(L.eonerf_mesh_dsm_rasterize(_ptr(vertices), n_v, _ptr(faces), n_t, scale, offset, xoff, yoff, xsize, ysize, res, _ptr(keys),
+                                               _ptr(dsm), _ptr(face), _ptr(counts), _stream()))
+        for name, a in tables.items():
+            out = torch.empty(ysize, xsize, a.shape[1], dtype=torch.float32, device=dev)
+            _lib.check(L.eonerf_mesh_dsm_attributes(_ptr(vertices), n_v, _ptr(faces), n_t, scale, offset, xoff, yoff, xsize, ysize, res,
+                                                    _ptr(face), _ptr(a), a.shape[1], _ptr(out), _stream()))
+            rasters[name] = out
+    if not (attributes or return_face or return_counts):
+        return dsm
+    result = {"dsm": dsm}
+    if attributes:
+        result["attributes"] = rasters
+    if return_face:
+        result["face"] = face
+    if return_counts:
+        result["counts"] = dict(zip(("rasterised", "dropped", "degenerate", "covered"), counts.tolist()))
+    return result
+
+
+@torch.no_grad()
+def evaluate_mesh_dsm(mesh, gt, roi, scene_offset, scene_scale, water=None, scaling=False, return_all=False):
+    """DSM MAE of a mesh against a lidar DSM, on the scale of dsm.evaluate_dsm: rasterize_mesh on the GT's grid (roi = x, y, size, res)
+    -> water mask -> registration -> MAE.  Returns device double[2] = MAE, n_valid (return_all: a dict with "mae", "err", "dsm",
+    "transform").  Nothing is read back."""
+    from .dsm import _raster, dsm_mae, mask_water, register_dsm
+    gt = _raster(gt)
+    dsm = rasterize_mesh(mesh, scene_offset, scene_scale, roi=roi)
+    if water is not None:
+        dsm = mask_water(dsm, water)
+    transform = register_dsm(gt, dsm, scaling=scaling)
+    out = dsm_mae(gt, dsm, transform, return_err=return_all)
+    if not return_all:
+        return out
+    return {"mae": out[0], "err": out[1], "dsm": dsm, "transform": transform}
 
 
 def _host(a):

@@ -39,7 +39,9 @@ normals and albedo).  `--mesh_level` is the density of the level set; its defaul
 a guess that has not been measured on a converged scene.  `--mesh_min_component N` drops every solid of fewer than N lattice points,
 `--mesh_keep_largest K` all but the K largest, `--mesh_fill_cavities` the closed inner surfaces no view can see
 (mesh.filter_components); all three are off by default -- a good N has not been measured -- and act only together with `--mesh_out`;
-with any of them the PLY also carries each vertex' component id.  Without the flag nothing changes.
+with any of them the PLY also carries each vertex' component id.  Together with `--gt_dsm` rank 0 then rasterises the mesh it saved
+straight from above on the lidar DSM's grid, registers it and prints `mesh/mae=` once (eonerf_code_amd.mesh.evaluate_mesh_dsm): the
+mesh on the scale of val/mae.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -252,6 +254,11 @@ def main():
                         print(f"step={step} | mesh_components={int(torch.unique(mesh['component']).numel())} | "
                               f"smallest_component={int(sizes.min()) if sizes.numel() else 0} | " +
                               " | ".join(f"{k}={v}" for k, v in mesh["report"].items()), flush=True)
+                    if gt is not None:                                      # the saved (filtered) mesh on the scale of val/mae
+                        from .mesh import evaluate_mesh_dsm
+                        mesh_mae, mesh_cells = evaluate_mesh_dsm(mesh, gt["dsm"], [float(x) for x in gt["roi"]], gt["scene_offset"],
+                                                                 gt["scene_scale"], water=gt["water"]).tolist()
+                        print(f"step={step} | mesh/mae={mesh_mae:.4f} | mesh/cells={int(mesh_cells)}", flush=True)
                 if args.dump_params:                                        # replica-equality checks of the tests
                     torch.save(field.flat_params().detach().cpu(), f"{args.dump_params}.rank{rank}")
                 if torch.distributed.is_initialized():
