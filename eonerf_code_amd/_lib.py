@@ -1,4 +1,4 @@
-"""ctypes binding of libeonerf_hip.so (include/eonerf_hip.h).
+"""ctypes binding of libeonerf_hip.so (the headers of include/): one table of the C ABI, the build, the load.
 
 PyTorch is plumbing here: it owns device memory (tensor.data_ptr()) and the current HIP stream; every arithmetic
 step of the hot path runs inside the HIP library.  There is NO fallback: if the library is missing, cannot be
@@ -16,48 +16,6 @@ EONERF_FP32, EONERF_BF16, EONERF_F16X3 = 0, 1, 2
 PRECISIONS = {"fp32": EONERF_FP32, "bf16": EONERF_BF16, "fp16x3": EONERF_F16X3}
 F_SHADOWS, F_EVAL, F_TRAIN, F_ONLY_DEPTH, F_RGB_LOSS = 1, 2, 4, 8, 16
 
-SYMBOLS = ["eonerf_version", "eonerf_strerror", "eonerf_create", "eonerf_destroy", "eonerf_param_tensors",
-           "eonerf_param_info", "eonerf_param_floats", "eonerf_set_weights", "eonerf_field_workspace_bytes",
-           "eonerf_render_workspace_bytes", "eonerf_field_forward", "eonerf_query_density", "eonerf_render_forward",
-           "eonerf_render_backward", "eonerf_adam_step", "eonerf_profile_enable", "eonerf_profile_read",
-           "eonerf_train_loss", "eonerf_sample_rays", "eonerf_rendering", "eonerf_generate_rays",
-           "eonerf_field_train_workspace_bytes", "eonerf_field_forward_train",
-           "eonerf_field_backward", "eonerf_set_noise_seed", "eonerf_render_status", "eonerf_device_status", "eonerf_grad_floats",
-           "eonerf_grad_seal", "eonerf_profile_name", "eonerf_adam_step_zero_grad", "eonerf_rendering_train", "eonerf_rendering_backward", "eonerf_clock_probe", "eonerf_range_status", "eonerf_set_n_samples", "eonerf_render_backward_loss",
-           "eonerf_presample", "eonerf_presample_cancel", "eonerf_grad_early_floats", "eonerf_set_exchange_event"]
-# include/eonerf_dsm.h: the stateless DSM evaluation group of the same library
-DSM_SYMBOLS = ["eonerf_dsm_version", "eonerf_nadir_rays", "eonerf_dsm_rasterize", "eonerf_dsm_mask_water",
-               "eonerf_dsm_register_workspace_bytes", "eonerf_dsm_register_levels", "eonerf_dsm_register_level",
-               "eonerf_dsm_register", "eonerf_dsm_mae_workspace_bytes", "eonerf_dsm_mae"]
-# include/eonerf_prior.h: the stateless depth-prior group (initial DSM -> per-ray depth / confidence)
-PRIOR_SYMBOLS = ["eonerf_prior_version", "eonerf_prior_workspace_bytes", "eonerf_prior_reproject"]
-# include/eonerf_metrics.h: the stateless per-image validation metrics (uncertainty loss, MSE, PSNR)
-METRICS_SYMBOLS = ["eonerf_metrics_version", "eonerf_metrics_workspace_bytes", "eonerf_image_metrics"]
-# include/eonerf_sweep.h: one view under K sun directions from one camera pass (relight.py)
-SWEEP_SYMBOLS = ["eonerf_sweep_version", "eonerf_sun_sweep_workspace_bytes", "eonerf_render_sun_sweep"]
-# include/eonerf_occ.h: the occupancy grid (occupancy.py) -- update, dilation, the grid of a context's export renders, the pinned sampler
-OCC_SYMBOLS = ["eonerf_occ_version", "eonerf_occ_workspace_bytes", "eonerf_occ_update", "eonerf_occ_dilate", "eonerf_set_occupancy",
-               "eonerf_occ_sample_rays"]
-# include/eonerf_march.h: block-wise early ray termination of export renders (sat_rendering.render_image(early_stop_eps=...))
-MARCH_SYMBOLS = ["eonerf_march_version", "eonerf_march_workspace_bytes", "eonerf_render_forward_march", "eonerf_march_sample_round"]
-# include/eonerf_quantile.h: quantile depth of export renders (sat_rendering.render_depth_quantiles)
-QUANTILE_SYMBOLS = ["eonerf_quantile_version", "eonerf_quantile_workspace_bytes", "eonerf_render_depth_quantiles"]
-# include/eonerf_ortho.h: the stateless true-orthophoto group (ortho.py): surface points, per-image gather, fusion
-ORTHO_SYMBOLS = ["eonerf_ortho_version", "eonerf_ortho_ground", "eonerf_ortho_gather", "eonerf_ortho_fuse"]
-# include/eonerf_pose.h: camera offset refinement (pose.py) -- the ray-origin gradient behind a render backward and its per-image sum
-POSE_SYMBOLS = ["eonerf_pose_version", "eonerf_origin_grad_scratch_bytes", "eonerf_render_origin_grad"]
-# include/eonerf_normals.h: the forward-mode density gradient and the surface normals of export renders (normals.py)
-NORMALS_SYMBOLS = ["eonerf_normals_version", "eonerf_density_grad_workspace_bytes", "eonerf_field_density_grad",
-                   "eonerf_normals_workspace_bytes", "eonerf_render_normals"]
-# include/eonerf_mesh.h: the stateless mesh export group (mesh.py) -- marching tetrahedra over a sampled density volume
-MESH_SYMBOLS = ["eonerf_mesh_version", "eonerf_mesh_lattice_points", "eonerf_mesh_workspace_bytes", "eonerf_mesh_count", "eonerf_mesh_emit"]
-# include/eonerf_components.h: connected components of a volume under the mesher's connectivity, and the floater / cavity filter (mesh.py)
-CC_SYMBOLS = ["eonerf_cc_version", "eonerf_cc_workspace_bytes", "eonerf_cc_label", "eonerf_cc_filter"]
-# include/eonerf_mesh_dsm.h: a mesh rasterised from above into a DSM, a face raster and attribute rasters (mesh.rasterize_mesh)
-MESH_DSM_SYMBOLS = ["eonerf_mesh_dsm_version", "eonerf_mesh_dsm_rasterize", "eonerf_mesh_dsm_attributes"]
-# include/eonerf_layout.h: the read-only workspace layout query (tests decode the saved slabs through it)
-LAYOUT_SYMBOLS = ["eonerf_layout_version", "eonerf_workspace_layout"]
-
 
 class EonerfRpc(C.Structure):
     _fields_ = [("col_num", C.c_double * 20), ("col_den", C.c_double * 20), ("row_num", C.c_double * 20), ("row_den", C.c_double * 20),
@@ -70,27 +28,166 @@ class EonerfConfig(C.Structure):
     _fields_ = [("n_images", C.c_int), ("precision", C.c_int), ("n_samples", C.c_int), ("radiometric", C.c_int)]
 
 
+# The whole C ABI: public header -> entry point -> (return type, argument types), one line per prototype.  lib() binds exactly this,
+# build() digests exactly these headers, and tests/test_library_abi.py holds every line against the header's prototype.
+vp, cp, i, lg, sz, fp, d = C.c_void_p, C.c_char_p, C.c_int, C.c_long, C.c_size_t, C.c_float, C.c_double
+i64, u32, u64 = C.c_int64, C.c_uint32, C.c_uint64
+f3, d3, rpc = C.POINTER(fp), C.POINTER(d), C.POINTER(EonerfRpc)
+API = {
+    # the context and the training / rendering entry points (radiance_fields/eonerf.py, trainer.py, sat_rendering.py, datasets/satellite.py)
+    "eonerf_hip.h": {
+        "eonerf_version": (i, []),
+        "eonerf_strerror": (cp, [i]),
+        "eonerf_create": (i, [C.POINTER(vp), C.POINTER(EonerfConfig)]),
+        "eonerf_destroy": (i, [vp]),
+        "eonerf_param_tensors": (i, [vp]),
+        "eonerf_param_info": (i, [vp, i, C.POINTER(cp), C.POINTER(sz), C.POINTER(i), C.POINTER(i)]),
+        "eonerf_param_floats": (sz, [vp]),
+        "eonerf_set_weights": (i, [vp, vp, vp]),
+        "eonerf_field_workspace_bytes": (sz, [vp, i]),
+        "eonerf_render_workspace_bytes": (sz, [vp, i, i]),
+        "eonerf_field_forward": (i, [vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "eonerf_query_density": (i, [vp, vp, vp, i, vp, vp, sz, vp]),
+        "eonerf_render_forward": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp, vp, sz, vp]),
+        "eonerf_render_backward": (i, [vp, vp, vp, vp, i, i, vp, vp, vp, sz, vp]),
+        "eonerf_adam_step": (i, [vp, vp, vp, vp, vp, i, fp, fp, fp, fp, fp, vp, vp]),
+        "eonerf_profile_enable": (i, [vp, i]),
+        "eonerf_profile_read": (i, [vp, i, f3, C.POINTER(i)]),
+        "eonerf_train_loss": (i, [vp, vp, vp, i, i, vp, vp, vp]),
+        "eonerf_sample_rays": (i, [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "eonerf_rendering": (i, [vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "eonerf_generate_rays": (i, [rpc, vp, vp, lg, i, d, d, i, i, d, d, f3, f3, vp, vp, vp, vp]),
+        "eonerf_field_train_workspace_bytes": (sz, [vp, i, i]),
+        "eonerf_field_forward_train": (i, [vp, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "eonerf_field_backward": (i, [vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "eonerf_set_noise_seed": (i, [vp, u64]),
+        "eonerf_render_status": (i, [vp, i, i, vp, sz, vp]),
+        "eonerf_device_status": (i, [vp, vp]),
+        "eonerf_grad_floats": (sz, [vp]),
+        "eonerf_grad_seal": (i, [vp, vp, vp]),
+        "eonerf_profile_name": (cp, [i]),
+        "eonerf_adam_step_zero_grad": (i, [vp, vp, vp, vp, vp, i, fp, fp, fp, fp, fp, vp, vp]),
+        "eonerf_rendering_train": (i, [vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "eonerf_rendering_backward": (i, [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "eonerf_clock_probe": (i, [vp, vp, vp]),
+        "eonerf_range_status": (i, [vp, vp]),
+        "eonerf_set_n_samples": (i, [vp, i]),
+        "eonerf_render_backward_loss": (i, [vp, vp, vp, vp, i, i, vp, vp, i, vp, vp, vp, vp, sz, vp]),
+        "eonerf_presample": (i, [vp, vp, vp, vp, i, i, vp, vp, sz, vp]),
+        "eonerf_presample_cancel": (i, [vp]),
+        "eonerf_grad_early_floats": (sz, [vp]),
+        "eonerf_set_exchange_event": (i, [vp, vp, i]),
+    },
+    # the stateless DSM evaluation group of the same library (dsm.py)
+    "eonerf_dsm.h": {
+        "eonerf_dsm_version": (i, []),
+        "eonerf_nadir_rays": (i, [i, i, d, d, d, d, d, d3, d, d, vp, vp]),
+        "eonerf_dsm_rasterize": (i, [vp, i, vp, lg, d3, d3, d, d, i, i, d, vp, vp, vp, vp]),
+        "eonerf_dsm_mask_water": (i, [vp, i, i, vp, i, i, vp]),
+        "eonerf_dsm_register_workspace_bytes": (sz, [i, i, i, i]),
+        "eonerf_dsm_register_levels": (i, [i, i]),
+        "eonerf_dsm_register_level": (i, [i, i, i, i, i, C.POINTER(i), C.POINTER(sz)]),
+        "eonerf_dsm_register": (i, [vp, i, i, vp, i, i, i, vp, vp, sz, vp]),
+        "eonerf_dsm_mae_workspace_bytes": (sz, []),
+        "eonerf_dsm_mae": (i, [vp, i, i, vp, i, i, vp, i, i, vp, vp, vp, vp, sz, vp]),
+    },
+    # the stateless depth-prior group (priors.py): initial DSM -> per-ray depth / confidence
+    "eonerf_prior.h": {
+        "eonerf_prior_version": (i, []),
+        "eonerf_prior_workspace_bytes": (sz, [i, i]),
+        "eonerf_prior_reproject": (i, [vp, vp, i, i, d3, rpc, i, i, i, i, vp, i, vp, i, fp, fp, vp, vp, sz, vp]),
+    },
+    # the stateless per-image validation metrics (validation.py): uncertainty loss, MSE, PSNR
+    "eonerf_metrics.h": {
+        "eonerf_metrics_version": (i, []),
+        "eonerf_metrics_workspace_bytes": (sz, []),
+        "eonerf_image_metrics": (i, [vp, i, vp, i, vp, i, lg, vp, vp, sz, vp]),
+    },
+    # one view under K sun directions from one camera pass (relight.py)
+    "eonerf_sweep.h": {
+        "eonerf_sweep_version": (i, []),
+        "eonerf_sun_sweep_workspace_bytes": (sz, [vp, i, i]),
+        "eonerf_render_sun_sweep": (i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]),
+    },
+    # the occupancy grid (occupancy.py): update, dilation, the grid of a context's export renders, the pinned sampler
+    "eonerf_occ.h": {
+        "eonerf_occ_version": (i, []),
+        "eonerf_occ_workspace_bytes": (sz, [vp, i]),
+        "eonerf_occ_update": (i, [vp, vp, vp, vp, i, fp, fp, fp, i, u32, vp, vp, vp, sz, vp]),
+        "eonerf_occ_dilate": (i, [vp, vp, i, vp]),
+        "eonerf_set_occupancy": (i, [vp, vp, i]),
+        "eonerf_occ_sample_rays": (i, [vp, vp, vp, vp, i, i, vp, i, vp, vp, vp, vp, vp, vp, sz, vp]),
+    },
+    # block-wise early ray termination of export renders (sat_rendering.render_image(early_stop_eps=...))
+    "eonerf_march.h": {
+        "eonerf_march_version": (i, []),
+        "eonerf_march_workspace_bytes": (sz, [vp, i, i, i]),
+        "eonerf_render_forward_march": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, fp, i, vp, vp, vp, vp, sz, vp]),
+        "eonerf_march_sample_round": (i, [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, sz, vp]),
+    },
+    # quantile depth of export renders (sat_rendering.render_depth_quantiles)
+    "eonerf_quantile.h": {
+        "eonerf_quantile_version": (i, []),
+        "eonerf_quantile_workspace_bytes": (sz, [vp, i, i, i]),
+        "eonerf_render_depth_quantiles": (i, [vp, vp, vp, vp, vp, vp, i, vp, i, fp, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    },
+    # the stateless true-orthophoto group (ortho.py): surface points, per-image gather, fusion
+    "eonerf_ortho.h": {
+        "eonerf_ortho_version": (i, []),
+        "eonerf_ortho_ground": (i, [vp, i, vp, lg, f3, f3, i, i, vp, vp]),
+        "eonerf_ortho_gather": (i, [vp, lg, rpc, vp, i, i, i, f3, f3, vp, fp, vp, vp, vp, vp]),
+        "eonerf_ortho_fuse": (i, [vp, vp, i, lg, i, i, vp, vp, vp, vp]),
+    },
+    # camera offset refinement (pose.py): the ray-origin gradient behind a render backward and its per-image sum
+    "eonerf_pose.h": {
+        "eonerf_pose_version": (i, []),
+        "eonerf_origin_grad_scratch_bytes": (sz, [vp, i, i]),
+        "eonerf_render_origin_grad": (i, [vp, vp, vp, vp, i, i, vp, sz, vp, sz, vp, vp, vp]),
+    },
+    # the forward-mode density gradient and the surface normals of export renders (normals.py)
+    "eonerf_normals.h": {
+        "eonerf_normals_version": (i, []),
+        "eonerf_density_grad_workspace_bytes": (sz, [vp, i]),
+        "eonerf_field_density_grad": (i, [vp, vp, vp, i, vp, vp, vp, sz, vp]),
+        "eonerf_normals_workspace_bytes": (sz, [vp, i]),
+        "eonerf_render_normals": (i, [vp, vp, vp, vp, vp, vp, i, f3, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    },
+    # the stateless mesh export group (mesh.py): marching tetrahedra over a sampled density volume
+    "eonerf_mesh.h": {
+        "eonerf_mesh_version": (i, []),
+        "eonerf_mesh_lattice_points": (i, [f3, f3, i, i, i, i, vp, vp]),
+        "eonerf_mesh_workspace_bytes": (sz, [i, i, i]),
+        "eonerf_mesh_count": (i, [vp, i, i, i, fp, vp, vp, sz, vp]),
+        "eonerf_mesh_emit": (i, [vp, i, i, i, fp, f3, f3, vp, sz, vp, i64, vp, i64, vp, vp, vp]),
+    },
+    # connected components of a volume under the mesher's connectivity, and the floater / cavity filter (mesh.py)
+    "eonerf_components.h": {
+        "eonerf_cc_version": (i, []),
+        "eonerf_cc_workspace_bytes": (sz, [i, i, i]),
+        "eonerf_cc_label": (i, [vp, i, i, i, fp, i, vp, vp, vp, vp, sz, vp]),
+        "eonerf_cc_filter": (i, [vp, vp, vp, i, i, i, i, i64, i, vp, vp, vp]),
+    },
+    # a mesh rasterised from above into a DSM, a face raster and attribute rasters (mesh.rasterize_mesh)
+    "eonerf_mesh_dsm.h": {
+        "eonerf_mesh_dsm_version": (i, []),
+        "eonerf_mesh_dsm_rasterize": (i, [vp, i64, vp, i64, d3, d3, d, d, i, i, d, vp, vp, vp, vp, vp]),
+        "eonerf_mesh_dsm_attributes": (i, [vp, i64, vp, i64, d3, d3, d, d, i, i, d, vp, vp, i, vp, vp]),
+    },
+    # the read-only workspace layout query (tests decode the saved slabs through it)
+    "eonerf_layout.h": {
+        "eonerf_layout_version": (i, []),
+        "eonerf_workspace_layout": (i, [vp, i, i, i, C.POINTER(u64), i]),
+    },
+}
+
+
 def build(verbose=False):
     """Compile libeonerf_hip.so in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     # up to date?  Decided by CONTENT (a digest of every source, kept beside the library), not by time stamps: a snapshot copied to the
     # GPU box may carry arbitrary mtimes, and the object files do not travel -- a current library must never be rebuilt there
     import hashlib
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h")) or f == "Makefile")
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_hip.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_dsm.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_prior.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_metrics.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_sweep.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_occ.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_march.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_quantile.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_ortho.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_pose.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_normals.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_mesh.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_components.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_mesh_dsm.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eonerf_layout.h"))
+    srcs += [os.path.join(_HERE, "..", "include", header) for header in API]
     h = hashlib.sha1()
     for f in srcs:
         with open(f, "rb") as fh:
@@ -133,132 +230,10 @@ def lib():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the EO-NeRF hot path has no non-HIP fallback)")
     L = C.CDLL(LIB_PATH)
-    vp, i, sz, fp = C.c_void_p, C.c_int, C.c_size_t, C.c_float
-    L.eonerf_version.restype = i
-    L.eonerf_strerror.restype = C.c_char_p
-    L.eonerf_strerror.argtypes = [i]
-    L.eonerf_create.argtypes = [C.POINTER(vp), C.POINTER(EonerfConfig)]
-    L.eonerf_destroy.argtypes = [vp]
-    L.eonerf_param_tensors.argtypes = [vp]
-    L.eonerf_param_info.argtypes = [vp, i, C.POINTER(C.c_char_p), C.POINTER(sz), C.POINTER(i), C.POINTER(i)]
-    L.eonerf_param_floats.restype = sz
-    L.eonerf_param_floats.argtypes = [vp]
-    L.eonerf_set_weights.argtypes = [vp, vp, vp]
-    L.eonerf_field_workspace_bytes.restype = sz
-    L.eonerf_field_workspace_bytes.argtypes = [vp, i]
-    L.eonerf_render_workspace_bytes.restype = sz
-    L.eonerf_render_workspace_bytes.argtypes = [vp, i, i]
-    L.eonerf_field_forward.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_query_density.argtypes = [vp, vp, vp, i, vp, vp, sz, vp]
-    L.eonerf_render_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp, vp, sz, vp]
-    L.eonerf_render_backward.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, sz, vp]
-    L.eonerf_presample.argtypes = [vp, vp, vp, vp, i, i, vp, vp, sz, vp]
-    L.eonerf_presample_cancel.argtypes = [vp]
-    L.eonerf_grad_early_floats.restype = sz
-    L.eonerf_grad_early_floats.argtypes = [vp]
-    L.eonerf_set_exchange_event.argtypes = [vp, vp, i]
-    L.eonerf_render_backward_loss.argtypes = [vp, vp, vp, vp, i, i, vp, vp, i, vp, vp, vp, vp, sz, vp]
-    L.eonerf_adam_step.argtypes = [vp, vp, vp, vp, vp, i, fp, fp, fp, fp, fp, vp, vp]
-    L.eonerf_adam_step_zero_grad.argtypes = [vp, vp, vp, vp, vp, i, fp, fp, fp, fp, fp, vp, vp]
-    L.eonerf_device_status.argtypes = [vp, vp]
-    L.eonerf_range_status.argtypes = [vp, vp]
-    L.eonerf_grad_floats.restype = sz
-    L.eonerf_grad_floats.argtypes = [vp]
-    L.eonerf_grad_seal.argtypes = [vp, vp, vp]
-    L.eonerf_field_train_workspace_bytes.restype = sz
-    L.eonerf_field_train_workspace_bytes.argtypes = [vp, i, i]
-    L.eonerf_field_forward_train.argtypes = [vp, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_field_backward.argtypes = [vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_render_status.argtypes = [vp, i, i, vp, sz, vp]
-    L.eonerf_train_loss.argtypes = [vp, vp, vp, i, i, vp, vp, vp]
-    L.eonerf_generate_rays.argtypes = [C.POINTER(EonerfRpc), vp, vp, C.c_long, i, C.c_double, C.c_double, i, i, C.c_double, C.c_double,
-                                       C.POINTER(fp), C.POINTER(fp), vp, vp, vp, vp]
-    L.eonerf_sample_rays.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_set_noise_seed.argtypes = [vp, C.c_uint64]
-    L.eonerf_set_n_samples.argtypes = [vp, i]
-    L.eonerf_rendering.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_rendering_train.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_rendering_backward.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_profile_enable.argtypes = [vp, i]
-    L.eonerf_profile_read.argtypes = [vp, i, C.POINTER(fp), C.POINTER(i)]
-    L.eonerf_clock_probe.argtypes = [vp, vp, vp]
-    L.eonerf_profile_name.restype = C.c_char_p
-    L.eonerf_profile_name.argtypes = [i]
-    d3 = C.POINTER(C.c_double)
-    L.eonerf_dsm_version.restype = i
-    L.eonerf_nadir_rays.argtypes = [i, i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, d3, C.c_double, C.c_double, vp, vp]
-    L.eonerf_dsm_rasterize.argtypes = [vp, i, vp, C.c_long, d3, d3, C.c_double, C.c_double, i, i, C.c_double, vp, vp, vp, vp]
-    L.eonerf_dsm_mask_water.argtypes = [vp, i, i, vp, i, i, vp]
-    L.eonerf_dsm_register_workspace_bytes.restype = sz
-    L.eonerf_dsm_register_workspace_bytes.argtypes = [i, i, i, i]
-    L.eonerf_dsm_register_levels.argtypes = [i, i]
-    L.eonerf_dsm_register_level.argtypes = [i, i, i, i, i, C.POINTER(i), C.POINTER(sz)]
-    L.eonerf_dsm_register.argtypes = [vp, i, i, vp, i, i, i, vp, vp, sz, vp]
-    L.eonerf_dsm_mae_workspace_bytes.restype = sz
-    L.eonerf_dsm_mae.argtypes = [vp, i, i, vp, i, i, vp, i, i, vp, vp, vp, vp, sz, vp]
-    L.eonerf_prior_version.restype = i
-    L.eonerf_prior_workspace_bytes.restype = sz
-    L.eonerf_prior_workspace_bytes.argtypes = [i, i]
-    L.eonerf_prior_reproject.argtypes = [vp, vp, i, i, d3, C.POINTER(EonerfRpc), i, i, i, i, vp, i, vp, i, fp, fp, vp, vp, sz, vp]
-    L.eonerf_metrics_version.restype = i
-    L.eonerf_metrics_workspace_bytes.restype = sz
-    L.eonerf_metrics_workspace_bytes.argtypes = []
-    L.eonerf_image_metrics.argtypes = [vp, i, vp, i, vp, i, C.c_long, vp, vp, sz, vp]
-    L.eonerf_sweep_version.restype = i
-    L.eonerf_sun_sweep_workspace_bytes.restype = sz
-    L.eonerf_sun_sweep_workspace_bytes.argtypes = [vp, i, i]
-    L.eonerf_render_sun_sweep.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
-    L.eonerf_occ_version.restype = i
-    L.eonerf_occ_workspace_bytes.restype = sz
-    L.eonerf_occ_workspace_bytes.argtypes = [vp, i]
-    L.eonerf_occ_update.argtypes = [vp, vp, vp, vp, i, fp, fp, fp, i, C.c_uint32, vp, vp, vp, sz, vp]
-    L.eonerf_occ_dilate.argtypes = [vp, vp, i, vp]
-    L.eonerf_set_occupancy.argtypes = [vp, vp, i]
-    L.eonerf_occ_sample_rays.argtypes = [vp, vp, vp, vp, i, i, vp, i, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_march_version.restype = i
-    L.eonerf_march_workspace_bytes.restype = sz
-    L.eonerf_march_workspace_bytes.argtypes = [vp, i, i, i]
-    L.eonerf_render_forward_march.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, fp, i, vp, vp, vp, vp, sz, vp]
-    L.eonerf_march_sample_round.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_quantile_version.restype = i
-    L.eonerf_quantile_workspace_bytes.restype = sz
-    L.eonerf_quantile_workspace_bytes.argtypes = [vp, i, i, i]
-    L.eonerf_render_depth_quantiles.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, fp, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_ortho_version.restype = i
-    f3 = C.POINTER(fp)
-    L.eonerf_ortho_ground.argtypes = [vp, i, vp, C.c_long, f3, f3, i, i, vp, vp]
-    L.eonerf_ortho_gather.argtypes = [vp, C.c_long, C.POINTER(EonerfRpc), vp, i, i, i, f3, f3, vp, fp, vp, vp, vp, vp]
-    L.eonerf_ortho_fuse.argtypes = [vp, vp, i, C.c_long, i, i, vp, vp, vp, vp]
-    L.eonerf_pose_version.restype = i
-    L.eonerf_origin_grad_scratch_bytes.restype = sz
-    L.eonerf_origin_grad_scratch_bytes.argtypes = [vp, i, i]
-    L.eonerf_render_origin_grad.argtypes = [vp, vp, vp, vp, i, i, vp, sz, vp, sz, vp, vp, vp]
-    L.eonerf_normals_version.restype = i
-    L.eonerf_density_grad_workspace_bytes.restype = sz
-    L.eonerf_density_grad_workspace_bytes.argtypes = [vp, i]
-    L.eonerf_field_density_grad.argtypes = [vp, vp, vp, i, vp, vp, vp, sz, vp]
-    L.eonerf_normals_workspace_bytes.restype = sz
-    L.eonerf_normals_workspace_bytes.argtypes = [vp, i]
-    L.eonerf_render_normals.argtypes = [vp, vp, vp, vp, vp, vp, i, f3, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.eonerf_mesh_version.restype = i
-    L.eonerf_mesh_lattice_points.argtypes = [f3, f3, i, i, i, i, vp, vp]
-    L.eonerf_mesh_workspace_bytes.restype = sz
-    L.eonerf_mesh_workspace_bytes.argtypes = [i, i, i]
-    L.eonerf_mesh_count.argtypes = [vp, i, i, i, fp, vp, vp, sz, vp]
-    L.eonerf_mesh_emit.argtypes = [vp, i, i, i, fp, f3, f3, vp, sz, vp, C.c_int64, vp, C.c_int64, vp, vp, vp]
-    L.eonerf_cc_version.restype = i
-    L.eonerf_cc_workspace_bytes.restype = sz
-    L.eonerf_cc_workspace_bytes.argtypes = [i, i, i]
-    L.eonerf_cc_label.argtypes = [vp, i, i, i, fp, i, vp, vp, vp, vp, sz, vp]
-    L.eonerf_cc_filter.argtypes = [vp, vp, vp, i, i, i, i, C.c_int64, i, vp, vp, vp]
-    L.eonerf_mesh_dsm_version.restype = i
-    L.eonerf_mesh_dsm_rasterize.argtypes = [vp, C.c_int64, vp, C.c_int64, d3, d3, C.c_double, C.c_double, i, i, C.c_double, vp, vp, vp, vp, vp]
-    L.eonerf_mesh_dsm_attributes.argtypes = [vp, C.c_int64, vp, C.c_int64, d3, d3, C.c_double, C.c_double, i, i, C.c_double, vp, vp, i, vp, vp]
-    L.eonerf_layout_version.restype = i
-    L.eonerf_workspace_layout.argtypes = [vp, i, i, i, C.POINTER(C.c_uint64), i]
-    for name in (SYMBOLS + DSM_SYMBOLS + PRIOR_SYMBOLS + METRICS_SYMBOLS + SWEEP_SYMBOLS + OCC_SYMBOLS + MARCH_SYMBOLS + QUANTILE_SYMBOLS
-                 + ORTHO_SYMBOLS + POSE_SYMBOLS + NORMALS_SYMBOLS + MESH_SYMBOLS + CC_SYMBOLS + MESH_DSM_SYMBOLS + LAYOUT_SYMBOLS):
-        getattr(L, name)
+    for group in API.values():
+        for name, (restype, argtypes) in group.items():
+            fn = getattr(L, name)               # resolves the symbol: a missing one fails here, at load
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -269,6 +244,17 @@ E_RANGE = -6
 def check(rc):
     if rc != 0:
         raise RuntimeError(f"libeonerf_hip: {lib().eonerf_strerror(rc).decode()} (code {rc})")
+
+
+def _ptr(t):
+    """The device address of a tensor as the void* the entry points take (None: NULL)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _stream():
+    """PyTorch's current HIP stream as the hipStream_t the entry points take."""
+    import torch                                # lazily: CPU tests import this module without touching torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def param_layout(ctx):

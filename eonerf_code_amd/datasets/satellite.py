@@ -85,7 +85,7 @@ def generate_rays(rpc, min_alt, max_alt, h=None, w=None, cols=None, rows=None, i
     import ctypes as C
     import torch
     from .. import _lib
-    from ..radiance_fields.eonerf import _ptr, _stream
+    from .._lib import _ptr, _stream
     s = _rpc_struct(rpc, img_downscale)
     dev = torch.device(device)
     if cols is not None:

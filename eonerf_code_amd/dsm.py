@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .radiance_fields.eonerf import _ptr, _stream
+from ._lib import _ptr, _stream
 
 
 def _d3(v):

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .radiance_fields.eonerf import _ptr, _stream
+from ._lib import _ptr, _stream
 
 UNIT_CUBE = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
 STATUS_CAPACITY = 1

@@ -13,9 +13,9 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import _ptr, _stream
 from .datasets.satellite import SatRays, namedtuple_map, satrays_to_table
 from .occupancy import OccupancyGrid, grid_on
-from .radiance_fields.eonerf import _ptr, _stream
 from .sat_rendering import _zsteps, n_samples_of
 
 

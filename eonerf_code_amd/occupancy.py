@@ -10,6 +10,7 @@ c >> 5: the uint32 words of the header, held in torch's int32).  `export_bits` i
 import torch
 
 from . import _lib
+from ._lib import _ptr, _stream
 
 AABB = (-1.0, -1.0, -1.0, 1.0, 1.0, 1.0)
 
@@ -150,11 +151,3 @@ class grid_on:
         if self.grid is not None:
             _lib.check(_lib.lib().eonerf_set_occupancy(self.native, None, 0))
         return False
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream

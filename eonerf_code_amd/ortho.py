@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .radiance_fields.eonerf import _ptr, _stream
+from ._lib import _ptr, _stream
 
 MAX_MEDIAN = 64      # EONERF_ORTHO_MAX_MEDIAN
 _MODES = {"mean": 0, "median": 1}

@@ -8,7 +8,7 @@ and the sun direction are not."""
 import torch
 
 from . import _lib
-from .radiance_fields.eonerf import _ptr, _stream
+from ._lib import _ptr, _stream
 
 
 def apply_origin_offsets(rays, img_idx, offsets):

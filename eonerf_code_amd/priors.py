@@ -11,7 +11,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .radiance_fields.eonerf import _ptr, _stream
+from ._lib import _ptr, _stream
+from .dsm import _raster as _dsm_raster
 
 
 def _reproject(dsm, values, bounds, rpc_struct, zone, south, out_h, out_w, want_raster, nan_fill, rays, z_offset, z_scale, depth_out=None):
@@ -30,11 +31,10 @@ def _reproject(dsm, values, bounds, rpc_struct, zone, south, out_h, out_w, want_
 
 
 def _raster(t, like=None):
-    if t.dim() != 2 or not t.is_cuda:
-        raise ValueError("a raster is a 2-D tensor on the GPU")
+    t = _dsm_raster(t)
     if like is not None and t.shape != like.shape:
         raise ValueError("the second raster must have the DSM's size (sat_utils.py:353)")
-    return t.to(torch.float32).contiguous()
+    return t
 
 
 def _zone(rpc_struct, zone, south):

@@ -12,15 +12,8 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._lib import _ptr, _stream
 from .mlp import MLP, DenseLayer, SinusoidalEncoder
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class _FieldFn(torch.autograd.Function):

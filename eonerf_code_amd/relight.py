@@ -9,9 +9,9 @@ whose columns 8..10 hold that sun.
 import torch
 
 from . import _lib
+from ._lib import _ptr, _stream
 from .datasets.satellite import SatRays, namedtuple_map, satrays_to_table, sun_direction
 from .occupancy import OccupancyGrid, grid_on
-from .radiance_fields.eonerf import _ptr, _stream
 from .sat_rendering import RESULT_SLICES, _zsteps, n_samples_of
 
 # the result keys that depend on the sun; every other key is the same for all suns and is returned once

@@ -13,10 +13,10 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import _ptr, _stream
 from .datasets.satellite import SatRays, namedtuple_map, satrays_to_table
 from .occupancy import OccupancyGrid, grid_on
 from .pose import apply_origin_offsets, origin_grad
-from .radiance_fields.eonerf import _ptr, _stream
 
 RESULT_SLICES = (("rgb", 0, 3), ("depth", 3, 4), ("albedo_rgb", 4, 7), ("ambient_rgb", 7, 10), ("geo_shadows", 10, 11),
                  ("transient_s", 11, 12), ("beta", 12, 13), ("entropy", 13, 14), ("pts_per_ray", 14, 15),

@@ -18,8 +18,9 @@ import os
 import torch
 
 from . import _lib
+from ._lib import _ptr, _stream
 from .pose import apply_origin_offsets, origin_grad
-from .radiance_fields.eonerf import EONerfMLP, _ptr, _stream
+from .radiance_fields.eonerf import EONerfMLP
 from .sat_rendering import _zsteps
 
 

@@ -10,7 +10,7 @@ import math
 import torch
 
 from . import _lib
-from .radiance_fields.eonerf import _ptr, _stream
+from ._lib import _ptr, _stream
 
 COLUMNS = ("loss", "coarse_color", "coarse_logbeta", "mse", "psnr", "mae", "n")
 

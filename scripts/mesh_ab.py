@@ -24,7 +24,7 @@ import torch
 from bf16_common import twin_train
 from eonerf_code_amd import _lib
 from eonerf_code_amd.mesh import UNIT_CUBE, density_volume, lattice_of, level_from_opacity, mesh_from_volume
-from eonerf_code_amd.radiance_fields.eonerf import _ptr, _stream
+from eonerf_code_amd._lib import _ptr, _stream
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)

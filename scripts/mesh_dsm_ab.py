@@ -25,7 +25,7 @@ from bf16_common import STEP, Z_SCALE, terrain_height, twin_train
 from eonerf_code_amd import _lib, dsm
 from eonerf_code_amd.datasets.satellite import define_satrays_from_tensors
 from eonerf_code_amd.mesh import density_volume, evaluate_mesh_dsm, filter_components, lattice_of, level_from_opacity, mesh_from_volume
-from eonerf_code_amd.radiance_fields.eonerf import _ptr, _stream
+from eonerf_code_amd._lib import _ptr, _stream
 from eonerf_code_amd.sat_rendering import render_image
 
 ap = argparse.ArgumentParser()

@@ -15,7 +15,8 @@ import torch
 
 from eonerf_code_amd import _lib
 from eonerf_code_amd.datasets.satellite import define_satrays_from_tensors
-from eonerf_code_amd.radiance_fields.eonerf import EONerfMLP, _ptr, _stream
+from eonerf_code_amd._lib import _ptr, _stream
+from eonerf_code_amd.radiance_fields.eonerf import EONerfMLP
 from eonerf_code_amd.relight import render_sun_sweep, sun_table
 from eonerf_code_amd.sat_rendering import render_image
 from eonerf_code_amd.synthetic import synthetic_batch

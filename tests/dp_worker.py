@@ -42,7 +42,8 @@ def main():
     torch.cuda.set_device(0)
     from oracle import eonerf_oracle as orc                       # test infrastructure: seeded weights / rays only
     from eonerf_code_amd import _lib
-    from eonerf_code_amd.radiance_fields.eonerf import EONerfMLP, _ptr, _stream
+    from eonerf_code_amd._lib import _ptr, _stream
+    from eonerf_code_amd.radiance_fields.eonerf import EONerfMLP
     from eonerf_code_amd.trainer import FusedTrainer, rank_slice
     n_img, R = 4, 256
     piped = mode in ("pipe", "pipedet", "fault", "nccl1", "pre0", "pre1", "pretog")

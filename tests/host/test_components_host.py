@@ -6,7 +6,6 @@ program labels and filters volumes from a file with a plain sequential union-fin
 for bit with the numpy restatement (tests/components_restated.py)."""
 import os
 import struct
-import subprocess
 import sys
 
 import numpy as np
@@ -18,26 +17,16 @@ for p in (REPO, os.path.join(REPO, "tests")):
         sys.path.insert(0, p)
 
 import components_restated as cr  # noqa: E402
-
-HIPCC = "/opt/rocm/bin/hipcc"
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+import sanitized  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("components_host") / "components_checks")
-    # host-only instrumentation: -fno-gpu-sanitize keeps the sanitizers off every device compilation, whatever the driver decides
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-           "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", os.path.join(REPO, "tests", "host", "components_checks.cpp"), "-o", path]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
-    return path
+    return sanitized.build(tmp_path_factory.mktemp("components_host") / "components_checks", "components_checks.cpp")
 
 
 def run(exe, args):
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=600, env=ENV)
-    assert r.returncode == 0 and "components checks ok" in r.stdout, r.stdout[-2000:] + r.stderr[-6000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    sanitized.run(exe, "components checks ok", args)
 
 
 def test_components_host_logic_under_asan_ubsan(exe):

@@ -6,7 +6,6 @@ tests/host/test_mesh_host.py builds mesh_checks.cpp, and run as a program.  The 
 and counts are compared bit for bit with the numpy restatement (tests/mesh_dsm_restated.py) on the cases of tests/mesh_dsm_cases.py."""
 import os
 import struct
-import subprocess
 import sys
 
 import numpy as np
@@ -20,26 +19,16 @@ for p in (REPO, os.path.join(REPO, "tests")):
 import mesh_dsm_cases as mc  # noqa: E402
 import mesh_dsm_restated as md  # noqa: E402
 import mesh_restated as mr  # noqa: E402
-
-HIPCC = "/opt/rocm/bin/hipcc"
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+import sanitized  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("mesh_dsm_host") / "mesh_dsm_checks")
-    # host-only instrumentation: -fno-gpu-sanitize keeps the sanitizers off every device compilation, whatever the driver decides
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-           "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", os.path.join(REPO, "tests", "host", "mesh_dsm_checks.cpp"), "-o", path]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
-    return path
+    return sanitized.build(tmp_path_factory.mktemp("mesh_dsm_host") / "mesh_dsm_checks", "mesh_dsm_checks.cpp")
 
 
 def run(exe, args):
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=600, env=ENV)
-    assert r.returncode == 0 and "mesh dsm checks ok" in r.stdout, r.stdout[-2000:] + r.stderr[-6000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    sanitized.run(exe, "mesh dsm checks ok", args)
 
 
 def test_mesh_dsm_host_logic_under_asan_ubsan(exe):

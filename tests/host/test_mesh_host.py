@@ -5,7 +5,6 @@ undefined-behaviour sanitizers, exactly as tests/host/test_normals_host.py build
 program meshes volumes from a file: its output is compared bit for bit with the numpy restatement (tests/mesh_restated.py)."""
 import os
 import struct
-import subprocess
 import sys
 
 import numpy as np
@@ -17,26 +16,16 @@ for p in (REPO, os.path.join(REPO, "tests")):
         sys.path.insert(0, p)
 
 import mesh_restated as mr  # noqa: E402
-
-HIPCC = "/opt/rocm/bin/hipcc"
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+import sanitized  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("mesh_host") / "mesh_checks")
-    # host-only instrumentation: -fno-gpu-sanitize keeps the sanitizers off every device compilation, whatever the driver decides
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-           "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", os.path.join(REPO, "tests", "host", "mesh_checks.cpp"), "-o", path]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
-    return path
+    return sanitized.build(tmp_path_factory.mktemp("mesh_host") / "mesh_checks", "mesh_checks.cpp")
 
 
 def run(exe, args):
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=600, env=ENV)
-    assert r.returncode == 0 and "mesh checks ok" in r.stdout, r.stdout[-2000:] + r.stderr[-6000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    sanitized.run(exe, "mesh checks ok", args)
 
 
 def test_mesh_host_logic_under_asan_ubsan(exe):

@@ -1,25 +1,8 @@
 """CPU: the sun sweep's workspace layout (carve_sweep, csrc/eonerf_carve.h) and its 64-bit ray bound, checked by the stand-alone
 program tests/host/sweep_checks.cpp built host-only under the address and undefined-behaviour sanitizers, exactly as
 tests/test_host_sanitizers.py builds host_checks.cpp, and run as a program."""
-import os
-import subprocess
-import sys
-
-REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-
-HIPCC = "/opt/rocm/bin/hipcc"
+import sanitized
 
 
 def test_carve_sweep_host_logic_under_asan_ubsan(tmp_path):
-    exe = str(tmp_path / "sweep_checks")
-    # host-only instrumentation: -fno-gpu-sanitize keeps the sanitizers off every device compilation, whatever the driver decides
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
-           "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", os.path.join(REPO, "tests", "host", "sweep_checks.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "sweep checks ok" in r.stdout, r.stdout[-2000:] + r.stderr[-6000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    sanitized.run(sanitized.build(tmp_path / "sweep_checks", "sweep_checks.cpp"), "sweep checks ok")

@@ -180,7 +180,7 @@ def test_extract_mesh_defaults_keep_their_bits_and_make_no_component_call(monkey
     assert lab["counts"][0] >= 2 and lab["counts"][2] < lab["counts"][1]
     calls = []
     L = _lib.lib()
-    for name in _lib.CC_SYMBOLS:
+    for name in _lib.API["eonerf_components.h"]:
         monkeypatch.setattr(L, name, (lambda name: lambda *a: calls.append(name))(name))
     plain = extract_mesh(f, resolution=n, level=level, bounds=bounds)
     explicit = extract_mesh(f, resolution=n, level=level, bounds=bounds, min_component_points=0, keep_largest=0, protect_boundary=False,

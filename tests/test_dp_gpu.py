@@ -277,7 +277,8 @@ def test_exchange_event_fires_where_the_early_block_is_final():
     that waits for the event copies the early block; the copy equals the block after the whole backward bit for bit, and the early block
     is exactly the trunk layers 1-4, 6, 7."""
     from eonerf_code_amd import _lib
-    from eonerf_code_amd.radiance_fields.eonerf import EONerfMLP, _ptr
+    from eonerf_code_amd._lib import _ptr
+    from eonerf_code_amd.radiance_fields.eonerf import EONerfMLP
     from eonerf_code_amd.trainer import FusedTrainer
     import ctypes as C
     sd = orc.random_state_dict(N_IMG, seed=91, bias_scale=0.05)

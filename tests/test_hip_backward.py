@@ -181,7 +181,7 @@ def test_backward_bf16_close_to_fp32_autograd():
 def test_adam_step_matches_torch():
     import ctypes as C
     from eonerf_code_amd import _lib
-    from eonerf_code_amd.radiance_fields.eonerf import _ptr, _stream
+    from eonerf_code_amd._lib import _ptr, _stream
     sd = orc.random_state_dict(3, seed=71)
     f = make_field(sd, 3, "fp32")
     flat = f.flat_params()

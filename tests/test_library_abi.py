@@ -1,22 +1,101 @@
-"""CPU: the C-ABI library builds for gfx950, loads, and exports every symbol include/eonerf_hip.h declares
-(no compute calls without a GPU)."""
+"""CPU: the C-ABI library builds for gfx950, loads, and exports every symbol the headers of include/ declare, and the ctypes table
+of eonerf_code_amd/_lib.py agrees with every prototype (no compute calls without a GPU)."""
 import ctypes
+import functools
 import os
 import re
 
+import pytest
+
 from conftest import REPO
+
+INCLUDE = os.path.join(REPO, "include")
+# prototypes per public header, written down here: a header or an entry point that appears or disappears is a decision, not a slip
+PROTOTYPES = {"eonerf_components.h": 4, "eonerf_dsm.h": 10, "eonerf_hip.h": 41, "eonerf_layout.h": 2, "eonerf_march.h": 4,
+              "eonerf_mesh.h": 5, "eonerf_mesh_dsm.h": 3, "eonerf_metrics.h": 3, "eonerf_normals.h": 5, "eonerf_occ.h": 6,
+              "eonerf_ortho.h": 4, "eonerf_pose.h": 3, "eonerf_prior.h": 3, "eonerf_quantile.h": 3, "eonerf_sweep.h": 3}
+C_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+             "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
+STRUCTS = {"eonerf_hip.h": {"eonerf_config": "EonerfConfig", "eonerf_rpc": "EonerfRpc"}}
+
+
+@functools.lru_cache(maxsize=None)
+def declarations(header):
+    """The header without comments and preprocessor lines -> ({name: (return type, [parameter, ...])}, {struct: [field declaration, ...]})."""
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
+    code = re.sub(r"^[ \t]*#.*$", "", code, flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([\w \t*]+?)\s*\b(eonerf_\w+)\s*\(([^()]*)\)\s*;", code):
+        assert name not in protos, name
+        params = [p.strip() for p in params.split(",")]
+        protos[name] = (ret.strip(), [] if params == ["void"] else params)
+    structs = {name: [f.strip() for f in body.split(";") if f.strip()] for body, name in re.findall(r"typedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;", code)}
+    return protos, structs
+
+
+def is_pointer(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def scalar(t):
+    """(kind, bytes) of a ctypes scalar: c_size_t is c_uint64 and c_long is c_int64 here, so identity would say nothing."""
+    assert isinstance(t, type) and issubclass(t, ctypes._SimpleCData) and not is_pointer(t), t
+    code = t._type_
+    return ("float" if code in "fd" else "signed" if code.islower() else "unsigned"), ctypes.sizeof(t)
+
+
+def agrees(c_decl, t, named=True):
+    """One C parameter (`const float* x`, `int n`, `double v[3]`) or return type (named=False) against one ctypes type."""
+    if "*" in c_decl or "[" in c_decl:
+        return is_pointer(t)
+    words = [w for w in c_decl.split() if w != "const"]
+    c_type = " ".join(words[:-1] if named else words)
+    if c_type == "void":
+        return t is None
+    return not is_pointer(t) and t is not None and scalar(C_SCALARS[c_type]) == scalar(t)
+
+
+@pytest.mark.parametrize("header", sorted(os.listdir(INCLUDE)))
+def test_bindings_table_agrees_with_the_header(header):
+    """_lib.API against include/<header>: the same names, exported and bound once, and per prototype the same number of parameters, a
+    pointer where the header has one, a scalar of the same kind and width where it has a scalar -- the return type included.  One
+    argument too few in a twenty-entry list would otherwise first show on the GPU, as a shifted pointer."""
+    from eonerf_code_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    assert set(_lib.API) == set(os.listdir(INCLUDE)) == set(PROTOTYPES)          # what build() digests: every public header, nothing else
+    protos, structs = declarations(header)
+    table = _lib.API[header]
+    assert set(protos) == set(table), set(protos) ^ set(table)
+    assert len(protos) == PROTOTYPES[header] and sum(PROTOTYPES.values()) == 99
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    for name, (ret, params) in protos.items():
+        assert [h for h in _lib.API if name in _lib.API[h]] == [header], name
+        assert [h for h in _lib.API if name in declarations(h)[0]] == [header], name
+        assert hasattr(L, name), name
+        restype, argtypes = table[name]
+        assert agrees(ret, restype, named=False), (name, ret, restype)
+        assert len(params) == len(argtypes), (name, len(params), len(argtypes))
+        for k, (p, t) in enumerate(zip(params, argtypes)):
+            assert agrees(p, t), (name, k, p, t)
+    assert set(structs) == set(STRUCTS.get(header, {}))
+    for struct, decls in structs.items():
+        fields = []                                         # `double a[20], b` -> (a, c_double, 20), (b, c_double, None)
+        for decl in decls:
+            c_type, names = decl.split(None, 1)
+            for n in names.split(","):
+                m = re.fullmatch(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*", n)
+                fields.append((m.group(1), scalar(C_SCALARS[c_type]), int(m.group(2)) if m.group(2) else None))
+        bound = [(n, scalar(t._type_), t._length_) if issubclass(t, ctypes.Array) else (n, scalar(t), None)
+                 for n, t in getattr(_lib, STRUCTS[header][struct])._fields_]
+        assert fields == bound, struct
 
 
 def test_header_symbols_exported():
     from eonerf_code_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
-    hdr = open(os.path.join(REPO, "include", "eonerf_hip.h")).read()
-    declared = set(re.findall(r"\b(eonerf_[a-z_]+)\s*\(", hdr))
     L = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(L, name), name
-    assert declared == set(_lib.SYMBOLS)
     L.eonerf_version.restype = ctypes.c_int
     assert L.eonerf_version() == 502
     L.eonerf_strerror.restype = ctypes.c_char_p

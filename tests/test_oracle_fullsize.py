@@ -206,7 +206,7 @@ def test_backward_through_a_multi_chunk_render_image_call(batch, precision, epoc
         grads.append({name: p.grad.detach().clone() for name, p in f.named_parameters() if p.grad is not None})
         outs.append((n, torch.cat([res[k] for k, _, _ in __import__("eonerf_code_amd.sat_rendering", fromlist=["x"]).RESULT_SLICES], dim=1)))
         from eonerf_code_amd import _lib
-        from eonerf_code_amd.radiance_fields.eonerf import _stream
+        from eonerf_code_amd._lib import _stream
         _lib.check(_lib.lib().eonerf_device_status(f._ctx, _stream()))
     assert outs[0][0] == outs[1][0] and torch.equal(outs[0][1], outs[1][1])
     for name, a in grads[0].items():

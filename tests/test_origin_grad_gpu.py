@@ -54,7 +54,7 @@ class Abi:
 
     def __init__(self, f, n, ns=128):
         from eonerf_code_amd import _lib
-        from eonerf_code_amd.radiance_fields.eonerf import _ptr, _stream
+        from eonerf_code_amd._lib import _ptr, _stream
         from eonerf_code_amd.sat_rendering import _zsteps
         self.lib, self.L, self.ptr, self.stream = _lib, _lib.lib(), _ptr, _stream
         self.f, self.n, self.ns = f, n, ns

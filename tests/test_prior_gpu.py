@@ -174,7 +174,7 @@ def test_refusals():
     import ctypes as C
     from eonerf_code_amd import _lib
     from eonerf_code_amd.datasets.satellite import _rpc_struct
-    from eonerf_code_amd.radiance_fields.eonerf import _ptr, _stream
+    from eonerf_code_amd._lib import _ptr, _stream
     L = _lib.lib()
     assert L.eonerf_prior_version() == 1
     c = R.make_case("tiny")

@@ -84,7 +84,7 @@ def test_adam_kernel_matches_torch_adam_with_zero_gradients_for_the_heads_outsid
     # parameters receive defined ZERO gradients (cat + slice), so torch.optim.Adam steps them from step 1 with a zero update and ONE
     # step count serves every parameter
     from eonerf_code_amd import _lib
-    from eonerf_code_amd.radiance_fields.eonerf import _ptr, _stream
+    from eonerf_code_amd._lib import _ptr, _stream
     f, tr, _ = _make()
     flat = tr.flat
     head = torch.zeros(flat.numel(), dtype=torch.bool)
@@ -137,7 +137,7 @@ def test_update_is_skipped_while_the_status_word_or_the_reduced_fault_flag_is_se
     # the fault gate of k_adam: a non-zero fault flag in the gradient message (what the all-reduce hands every rank when ANY rank
     # sealed a fault) skips the update, raises the local status word, and the status stays up until it has been read
     from eonerf_code_amd import _lib
-    from eonerf_code_amd.radiance_fields.eonerf import _ptr, _stream
+    from eonerf_code_amd._lib import _ptr, _stream
     f, tr, _ = _make()
     rays, img, pix, noise = _batch()
     tr.forward_backward(rays, img, pix, 3, noise=noise)
@@ -236,7 +236,7 @@ def test_lean_step_consumes_the_message_and_matches_the_kept_message_path(monkey
     rays, img, pix, noise = _batch(seed=72)
     # a fault: the lean path skips the update through the status word alone and still hands back a clean message
     from eonerf_code_amd import _lib
-    from eonerf_code_amd.radiance_fields.eonerf import _ptr, _stream
+    from eonerf_code_amd._lib import _ptr, _stream
     tr2.forward_backward(rays, img, pix, 3, noise=noise)
     flag = torch.ones(1, device="cuda")
     p0 = tr2.flat.detach().clone()
