@@ -180,6 +180,19 @@ API = {
     },
 }
 
+# Staged groups: their headers lie in csrc/ (build() digests every header there) until a follow-up moves them into include/ and their
+# tables into API.  lib() binds them after API; tests/test_simplify_abi_cpu.py holds every line against the header's prototype.
+i3 = C.POINTER(i)
+API_STAGED = {
+    # mesh simplification by vertex clustering (mesh.simplify_mesh)
+    "eonerf_simplify.h": {
+        "eonerf_simplify_version": (i, []),
+        "eonerf_simplify_workspace_bytes": (sz, [i3, i64, i64]),
+        "eonerf_simplify_count": (i, [vp, i64, vp, i64, f3, f3, i3, vp, sz, vp, vp]),
+        "eonerf_simplify_emit": (i, [vp, i64, vp, i64, f3, f3, i3, i, vp, sz, vp, i64, vp, i64, vp, vp, vp, vp]),
+    },
+}
+
 
 def build(verbose=False):
     """Compile libeonerf_hip.so in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -230,7 +243,7 @@ def lib():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the EO-NeRF hot path has no non-HIP fallback)")
     L = C.CDLL(LIB_PATH)
-    for group in API.values():
+    for group in list(API.values()) + list(API_STAGED.values()):
         for name, (restype, argtypes) in group.items():
             fn = getattr(L, name)               # resolves the symbol: a missing one fails here, at load
             fn.restype, fn.argtypes = restype, argtypes

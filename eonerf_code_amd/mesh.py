@@ -17,8 +17,13 @@ surface under the cell's centre, the face that gave it and per-vertex attributes
 component ids).  evaluate_mesh_dsm sends that raster through dsm.mask_water -> register_dsm -> dsm_mae, which puts a mesh -- and with it the
 level and every clean-up filter -- on the scale of the validation DSM MAE.
 
+simplify_mesh (csrc/eonerf_simplify.h, a staged header) clusters the vertices of a mesh on a coarse grid: all vertices of a cell become
+one -- the cell's mean, or the input vertex nearest to it -- and triangles that lose a corner to a merge disappear.  A pure,
+bit-reproducible function of its input; extract_mesh(simplify=k) runs it with cells of k lattice spacings in front of normals and albedo.
+Off by default: what it costs in DSM MAE on a converged scene has not been measured.
+
 Not here: marching cubes, vertex refinement along the gradient, filters on area or height above ground, labelling of the mesh graph
-itself, simplification and welding, textures, skipping empty space through the occupancy grid while the volume is filled, volumes larger
+itself, edge collapse, quadric error representatives, welding by distance, removal of duplicate triangles, textures, skipping empty space through the occupancy grid while the volume is filled, volumes larger
 than one call, OBJ / glTF writers.
 The default level of extract_mesh is a guess: it has not been measured on a converged scene, and neither has the quality of the mesh.
 """
@@ -269,10 +274,18 @@ def vertex_albedo(field, vertices, chunk=1 << 20):
     return torch.cat(out, dim=0) if out else vertices.new_empty(0, 3)
 
 
+class MeshDict(dict):
+    """The dict extract_mesh and simplify_mesh return.  Its keys are the mesh; what simplify_mesh(factor=...) needs to lay its grid over
+    the lattice the mesh came from rides along as attributes, not as keys: `lattice` = {"origin": fp32 triple, "spacing": fp32 triple,
+    "shape": (nz, ny, nx)} and `scene` = (scene_scale, scene_offset) as fp64 tensors, or None."""
+    lattice = None
+    scene = None
+
+
 @torch.no_grad()
 def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offset=None, scene_scale=None, normals=True, albedo=True,
                  slab_points=1 << 22, chunk=1 << 20, min_component_points=0, keep_largest=0, protect_boundary=False, fill_cavities=False,
-                 components=False):
+                 components=False, simplify=0, representative="mean"):
     """Mesh of the level set `level` of the field's density on a resolution^3 lattice over `bounds` (scene coordinates: the normalised
     cube).  Returns a dict: "vertices" fp32 [V, 3] in scene coordinates; "faces" int32 [T, 3], normals out of the dense side; "level";
     "normals" fp32 [V, 3]: -grad sigma at the vertices (normals.density_gradient, times 1 / scene_scale when that is given: the metric
@@ -283,7 +296,11 @@ def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offs
     min_component_points, keep_largest, protect_boundary, fill_cavities: filter_components on the volume in front of the extraction;
     the dict then also carries its "report".  All off by default (no component call is made, the result keeps today's bits): what a
     good min_component_points is has not been measured.  components: also "component" int32 [V], the root id of each vertex' solid
-    (label_components of the volume that was meshed), and "component_points" int32 [V], that solid's lattice points."""
+    (label_components of the volume that was meshed), and "component_points" int32 [V], that solid's lattice points.
+    simplify=k > 0: simplify_mesh with cells of k lattice spacings and `representative` ("mean" or "nearest") runs on the extracted mesh
+    BEFORE normals and albedo, which the field then gives at the V' new vertices (fewer points, and right for mean positions);
+    "component" and "component_points" go through "source".  The dict then also carries "source" int64 [V'] (the extracted vertex each
+    new one stands for) and "simplify" (simplify_mesh's report).  0: no simplify call is made and the result keeps today's bits."""
     from .normals import _axis_scale, density_gradient
     if level is None:
         level = level_from_opacity(0.5, 2.0 / 128)
@@ -302,7 +319,16 @@ def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offs
     else:
         vertices, faces = mesh_from_volume(volume, level, origin, spacing)
     del volume
-    mesh = {"vertices": vertices, "faces": faces, "level": float(level), **cleanup}
+    mesh = MeshDict({"vertices": vertices, "faces": faces, "level": float(level), **cleanup})
+    mesh.lattice = {"origin": tuple(origin), "spacing": tuple(spacing), "shape": tuple(int(n) for n in shape)}
+    if scene_offset is not None and scene_scale is not None:
+        mesh.scene = (torch.as_tensor(scene_scale, dtype=torch.float64).reshape(3).to(vertices.device),
+                      torch.as_tensor(scene_offset, dtype=torch.float64).reshape(3).to(vertices.device))
+    if simplify:
+        small = simplify_mesh(mesh, factor=simplify, representative=representative)
+        mesh.update(vertices=small["vertices"], faces=small["faces"], source=small["source"], simplify=small["report"])
+        mesh.update({k: small[k] for k in ("component", "component_points") if k in small})
+        vertices, faces = mesh["vertices"], mesh["faces"]
     if normals:
         axis = _axis_scale(scene_scale)
         grads = [density_gradient(field, vertices[i:i + chunk])[1] for i in range(0, vertices.shape[0], chunk)]
@@ -325,6 +351,113 @@ def _mesh_arrays(mesh):
     if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError("vertices [V, 3] and faces [T, 3]")
     return vertices.detach().float().contiguous(), faces.detach().to(torch.int32).contiguous()
+
+
+REPRESENTATIVES = {"mean": 0, "nearest": 1}
+PER_VERTEX = ("normals", "albedo", "component", "component_points")        # tables simplify_mesh gathers through "source"
+SIMPLIFY_MAX_DIM = 4096
+
+
+def _triple(value, what):
+    values = [float(value)] * 3 if isinstance(value, (int, float)) else [float(v) for v in value]
+    if len(values) != 3:
+        raise ValueError(f"{what}={value!r}: one number or three")
+    return values
+
+
+@torch.no_grad()
+def simplify_mesh(mesh, cell=None, factor=None, origin=None, dims=None, representative="mean", return_map=False):
+    """The mesh with its vertices clustered on a grid, by the rule of csrc/eonerf_simplify.h: all vertices of a cell become one, a
+    triangle with two corners in one cell disappears, every other triangle keeps its place, orientation and rotation.  Bit-reproducible:
+    the result does not depend on the order in which the device visits vertices or triangles.
+    mesh: a dict of extract_mesh, or a (vertices, faces) pair, on the GPU.
+    The grid: either factor=k with a dict of extract_mesh -- cells of k lattice spacings anchored on the lattice origin, one more per
+    axis than reach the lattice's last point -- or cell= (one size or three) with origin= (default: the lower corner of the finite
+    vertices' bounding box) and dims= (default: what covers the bounding box; at most 4096 per axis and 2^27 cells in all, vertices
+    outside the grid fall into its border cells).
+    representative: "mean" -- a new vertex is the mean of its cell's vertices (to 2^-14 of a cell) -- or "nearest" -- the input vertex
+    nearest to that mean, copied, at equal distance the one with the smallest index.
+    Returns a dict: "vertices" fp32 [V', 3]; "faces" int32 [T', 3]; "source" int64 [V']: the input vertex each new one stands for (the
+    nearest to the mean in both modes); "report": the counts (vertices_in, faces_in, vertices, faces, dropped, collapsed) and the grid
+    (origin, cell, dims, representative); with return_map "vertex_map" int32 [V]: the new index of every input vertex, -1 for one with a
+    coordinate that is not finite.  Every per-vertex table of an input dict ("normals", "albedo", "component", "component_points") is
+    gathered through "source"; "vertices_utm" too under "nearest", and under "mean" it is computed again from the new vertices (a dict
+    of extract_mesh knows its scene transform); "level" is kept.  One host synchronisation: the read-back of the counts."""
+    if representative not in REPRESENTATIVES:
+        raise ValueError(f"representative={representative!r}: 'mean' or 'nearest'")
+    vertices, faces = _mesh_arrays(mesh)
+    dev = vertices.device
+    n_v, n_t = vertices.shape[0], faces.shape[0]
+    lattice = getattr(mesh, "lattice", None)
+    if (cell is None) == (factor is None):
+        raise ValueError("simplify_mesh needs exactly one of cell= and factor=")
+    if factor is not None:
+        if lattice is None or origin is not None or dims is not None:
+            raise ValueError("factor= lays the grid over the lattice of an extract_mesh dict (and takes no origin= or dims=); give cell= for any other mesh")
+        if not float(factor) > 0:
+            raise ValueError(f"factor={factor!r}: a positive number of lattice spacings")
+        origin = lattice["origin"]
+        cell = [float(sp) * float(factor) for sp in lattice["spacing"]]
+        nz, ny, nx = lattice["shape"]
+        dims = [int(math.floor((n - 1) / float(factor))) + 1 for n in (nx, ny, nz)]
+    cell = _f3(_triple(cell, "cell"), "cell")
+    if not all(v > 0 for v in cell):
+        raise ValueError(f"cell={tuple(cell)!r}: every cell size must be positive")
+    if origin is None or dims is None:                      # the bounding box of the finite vertices: one more read-back
+        finite = vertices[torch.isfinite(vertices).all(dim=1)]
+        lo = finite.min(dim=0).values.tolist() if finite.shape[0] else [0.0, 0.0, 0.0]
+        hi = finite.max(dim=0).values.tolist() if finite.shape[0] else lo
+        if origin is None:
+            origin = lo
+        if dims is None:
+            dims = [min(max(int(math.floor((h - float(o)) / c)) + 1, 1), SIMPLIFY_MAX_DIM) for h, o, c in zip(hi, _triple(origin, "origin"), cell)]
+    origin = _f3(_triple(origin, "origin"), "origin")
+    dims = (C.c_int * 3)(*[int(d) for d in dims])
+    L = _lib.lib()
+    nb = L.eonerf_simplify_workspace_bytes(dims, n_v, n_t)
+    if not nb:
+        raise ValueError(f"dims={tuple(dims)!r}: each of 1 .. {SIMPLIFY_MAX_DIM}, at most 2^27 cells in all (larger cells, or a grid of its own)")
+    if n_v == 0:
+        vertices = torch.zeros(1, 3, dtype=torch.float32, device=dev)          # the library takes no null pointer
+    if n_t == 0:
+        faces = torch.zeros(1, 3, dtype=torch.int32, device=dev)
+    mode = REPRESENTATIVES[representative]
+    with torch.cuda.device(dev):
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        _lib.check(L.eonerf_simplify_count(_ptr(vertices), n_v, _ptr(faces), n_t, origin, cell, dims, _ptr(ws), nb, _ptr(counts), _stream()))
+        n_out, kept, dropped, collapsed = counts.tolist()          # the host synchronisation
+        out_v = torch.empty(max(n_out, 1), 3, dtype=torch.float32, device=dev)
+        out_t = torch.empty(max(kept, 1), 3, dtype=torch.int32, device=dev)
+        source = torch.empty(max(n_out, 1), dtype=torch.int32, device=dev)
+        vertex_map = torch.empty(max(n_v, 1), dtype=torch.int32, device=dev) if return_map else None
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(L.eonerf_simplify_emit(_ptr(vertices), n_v, _ptr(faces), n_t, origin, cell, dims, mode, _ptr(ws), nb, _ptr(out_v), n_out, _ptr(out_t),
+                                          kept, _ptr(source), _ptr(vertex_map), _ptr(status), _stream()))
+        if int(status.item()) & STATUS_CAPACITY:
+            raise RuntimeError("simplify_mesh: the emit call found more vertices or triangles than the count call (the mesh changed in between?)")
+    source = source[:n_out].long()
+    out = MeshDict({"vertices": out_v[:n_out], "faces": out_t[:kept], "source": source})
+    out["report"] = {"vertices_in": n_v, "faces_in": n_t, "vertices": n_out, "faces": kept, "dropped": dropped, "collapsed": collapsed,
+                     "origin": tuple(origin), "cell": tuple(cell), "dims": tuple(dims), "representative": representative}
+    if return_map:
+        out["vertex_map"] = vertex_map[:n_v]
+    if isinstance(mesh, dict):
+        out.lattice, out.scene = lattice, getattr(mesh, "scene", None)
+        if "level" in mesh:
+            out["level"] = mesh["level"]
+        for name in PER_VERTEX:
+            if mesh.get(name) is not None:
+                out[name] = mesh[name][source]
+        if mesh.get("vertices_utm") is not None:
+            if mode == REPRESENTATIVES["nearest"]:
+                out["vertices_utm"] = mesh["vertices_utm"][source]
+            elif out.scene is not None:
+                out["vertices_utm"] = out["vertices"].double() * out.scene[0] + out.scene[1]
+            else:
+                raise ValueError("simplify_mesh: 'vertices_utm' under representative='mean' has to be computed again from the new vertices, and only a dict of "
+                                 "extract_mesh knows its scene transform; drop the key, or use representative='nearest'")
+    return out
 
 
 @torch.no_grad()

@@ -39,9 +39,12 @@ normals and albedo).  `--mesh_level` is the density of the level set; its defaul
 a guess that has not been measured on a converged scene.  `--mesh_min_component N` drops every solid of fewer than N lattice points,
 `--mesh_keep_largest K` all but the K largest, `--mesh_fill_cavities` the closed inner surfaces no view can see
 (mesh.filter_components); all three are off by default -- a good N has not been measured -- and act only together with `--mesh_out`;
-with any of them the PLY also carries each vertex' component id.  Together with `--gt_dsm` rank 0 then rasterises the mesh it saved
-straight from above on the lidar DSM's grid, registers it and prints `mesh/mae=` once (eonerf_code_amd.mesh.evaluate_mesh_dsm): the
-mesh on the scale of val/mae.  Without the flag nothing changes.
+with any of them the PLY also carries each vertex' component id.  `--mesh_simplify K` (with `--mesh_representative mean|nearest`,
+default mean) clusters the mesh's vertices on cells of K lattice spacings before normals and albedo are taken (mesh.simplify_mesh); the
+status line then also shows the counts before, `vertices_in=` and `faces_in=`.  It is off by default -- what it costs in DSM MAE on a
+converged scene has not been measured -- and acts only together with `--mesh_out`.  Together with `--gt_dsm` rank 0 then rasterises
+the mesh it saved (filtered, simplified) straight from above on the lidar DSM's grid, registers it and prints `mesh/mae=` once
+(eonerf_code_amd.mesh.evaluate_mesh_dsm): the mesh on the scale of val/mae.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -96,6 +99,8 @@ def main():
     ap.add_argument("--mesh_min_component", type=int, default=0, help="drop solids of fewer lattice points from the mesh (0: keep all; only with --mesh_out)")
     ap.add_argument("--mesh_keep_largest", type=int, default=0, help="keep the K largest solids of the mesh, ties included (0: keep all; only with --mesh_out)")
     ap.add_argument("--mesh_fill_cavities", action="store_true", help="drop closed inner surfaces from the mesh (only with --mesh_out)")
+    ap.add_argument("--mesh_simplify", type=int, default=0, help="cluster the mesh's vertices on cells of K lattice spacings (0: off; only with --mesh_out)")
+    ap.add_argument("--mesh_representative", choices=["mean", "nearest"], default="mean", help="a cell's vertex: the mean of its vertices, or the one nearest to it")
     ap.add_argument("--rpc_correction", action="store_true", help="learn a 3-D offset per image, added to that image's ray origins (opt.py:80); single process only")
     ap.add_argument("--rpc_lr", type=float, default=None, help="learning rate of the offsets (default: --lr)")
     ap.add_argument("--resume", default=None, help="checkpoint to continue from (weights, optimizer state and, with --rpc_correction, the offsets)")
@@ -244,11 +249,13 @@ def main():
                     from .mesh import extract_mesh, save_ply
                     cleaned = bool(args.mesh_min_component or args.mesh_keep_largest or args.mesh_fill_cavities)
                     mesh = extract_mesh(field, resolution=args.mesh_res, level=args.mesh_level, min_component_points=args.mesh_min_component,
-                                        keep_largest=args.mesh_keep_largest, fill_cavities=args.mesh_fill_cavities, components=cleaned)
+                                        keep_largest=args.mesh_keep_largest, fill_cavities=args.mesh_fill_cavities, components=cleaned,
+                                        simplify=args.mesh_simplify, representative=args.mesh_representative)
                     os.makedirs(os.path.dirname(os.path.abspath(args.mesh_out)), exist_ok=True)
                     save_ply(args.mesh_out, mesh)
                     print(f"step={step} | mesh={args.mesh_out} | vertices={mesh['vertices'].shape[0]} | faces={mesh['faces'].shape[0]} | "
-                          f"level={mesh['level']:.6g}", flush=True)
+                          f"level={mesh['level']:.6g}" +
+                          (f" | vertices_in={mesh['simplify']['vertices_in']} | faces_in={mesh['simplify']['faces_in']}" if args.mesh_simplify else ""), flush=True)
                     if cleaned:
                         sizes = mesh["component_points"]
                         print(f"step={step} | mesh_components={int(torch.unique(mesh['component']).numel())} | "
