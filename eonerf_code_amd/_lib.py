@@ -192,6 +192,18 @@ API_STAGED = {
         "eonerf_simplify_emit": (i, [vp, i64, vp, i64, f3, f3, i3, i, vp, sz, vp, i64, vp, i64, vp, vp, vp, vp]),
     },
 }
+# A table of its own (tests/test_simplify_abi_cpu.py pins the set of headers in API_STAGED); tests/test_smooth_abi_cpu.py holds it to
+# the header.  lib() binds it after API_STAGED.
+i32p = C.POINTER(C.c_int32)
+API_STAGED_SMOOTH = {
+    # Taubin lambda|mu smoothing in fixed point (mesh.smooth_mesh)
+    "eonerf_smooth.h": {
+        "eonerf_smooth_version": (i, []),
+        "eonerf_smooth_workspace_bytes": (sz, [i64, i64]),
+        "eonerf_smooth_build": (i, [vp, i64, vp, i64, f3, f3, vp, i, vp, sz, vp, vp]),
+        "eonerf_smooth_run": (i, [vp, i64, i64, f3, f3, i32p, i, vp, sz, vp, vp, vp]),
+    },
+}
 
 
 def build(verbose=False):
@@ -243,7 +255,7 @@ def lib():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the EO-NeRF hot path has no non-HIP fallback)")
     L = C.CDLL(LIB_PATH)
-    for group in list(API.values()) + list(API_STAGED.values()):
+    for group in list(API.values()) + list(API_STAGED.values()) + list(API_STAGED_SMOOTH.values()):
         for name, (restype, argtypes) in group.items():
             fn = getattr(L, name)               # resolves the symbol: a missing one fails here, at load
             fn.restype, fn.argtypes = restype, argtypes

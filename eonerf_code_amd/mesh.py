@@ -22,7 +22,16 @@ one -- the cell's mean, or the input vertex nearest to it -- and triangles that 
 bit-reproducible function of its input; extract_mesh(simplify=k) runs it with cells of k lattice spacings in front of normals and albedo.
 Off by default: what it costs in DSM MAE on a converged scene has not been measured.
 
-Not here: marching cubes, vertex refinement along the gradient, filters on area or height above ground, labelling of the mesh graph
+smooth_mesh (csrc/eonerf_smooth.h, a staged header) runs Taubin's lambda|mu iteration of the face-weighted umbrella operator on positions
+in fixed point (2^-16 of a unit -- for a mesh of extract_mesh a lattice spacing): a Laplacian step with factor lambda > 0, then one with
+mu < -lambda, so the surface loses the roughness marching tetrahedra leave at the scale of one spacing without shrinking.  It keeps
+every vertex, every face and their order, so every per-vertex table stays valid; vertices on an open boundary stay where they are unless
+pin_open=False.  Every sum is an integer sum: a pure, bit-reproducible function of its input.  extract_mesh(smooth=k) runs k iterations
+after the extraction and in front of simplify, normals and albedo.  Off by default: what it does to the DSM MAE of a trained field is
+in profiles/smooth_ab.txt, not in a default.
+
+Not here: cotangent or area weights, bilateral or feature-preserving filters, implicit smoothing, re-projection onto the level set,
+sliding open vertices along their boundary, marching cubes, vertex refinement along the gradient, filters on area or height above ground, labelling of the mesh graph
 itself, edge collapse, quadric error representatives, welding by distance, removal of duplicate triangles, textures, skipping empty space through the occupancy grid while the volume is filled, volumes larger
 than one call, OBJ / glTF writers.
 The default level of extract_mesh is a guess: it has not been measured on a converged scene, and neither has the quality of the mesh.
@@ -285,7 +294,7 @@ class MeshDict(dict):
 @torch.no_grad()
 def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offset=None, scene_scale=None, normals=True, albedo=True,
                  slab_points=1 << 22, chunk=1 << 20, min_component_points=0, keep_largest=0, protect_boundary=False, fill_cavities=False,
-                 components=False, simplify=0, representative="mean"):
+                 components=False, simplify=0, representative="mean", smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
     """Mesh of the level set `level` of the field's density on a resolution^3 lattice over `bounds` (scene coordinates: the normalised
     cube).  Returns a dict: "vertices" fp32 [V, 3] in scene coordinates; "faces" int32 [T, 3], normals out of the dense side; "level";
     "normals" fp32 [V, 3]: -grad sigma at the vertices (normals.density_gradient, times 1 / scene_scale when that is given: the metric
@@ -300,7 +309,11 @@ def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offs
     simplify=k > 0: simplify_mesh with cells of k lattice spacings and `representative` ("mean" or "nearest") runs on the extracted mesh
     BEFORE normals and albedo, which the field then gives at the V' new vertices (fewer points, and right for mean positions);
     "component" and "component_points" go through "source".  The dict then also carries "source" int64 [V'] (the extracted vertex each
-    new one stands for) and "simplify" (simplify_mesh's report).  0: no simplify call is made and the result keeps today's bits."""
+    new one stands for) and "simplify" (simplify_mesh's report).  0: no simplify call is made and the result keeps today's bits.
+    smooth=k > 0: k lambda|mu iterations of smooth_mesh (factors smooth_lambda, smooth_mu; units of one lattice spacing) move the
+    extracted vertices after the component ids are taken and BEFORE simplify, normals and albedo, which the field then gives at the moved
+    vertices.  The dict then also carries "smooth" (smooth_mesh's report).  0: no smoothing call is made and the result keeps today's
+    bits and keys."""
     from .normals import _axis_scale, density_gradient
     if level is None:
         level = level_from_opacity(0.5, 2.0 / 128)
@@ -324,6 +337,10 @@ def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offs
     if scene_offset is not None and scene_scale is not None:
         mesh.scene = (torch.as_tensor(scene_scale, dtype=torch.float64).reshape(3).to(vertices.device),
                       torch.as_tensor(scene_offset, dtype=torch.float64).reshape(3).to(vertices.device))
+    if smooth:
+        moved = smooth_mesh(mesh, iterations=smooth, lam=smooth_lambda, mu=smooth_mu)
+        mesh.update(vertices=moved["vertices"], smooth=moved["report"])
+        vertices = mesh["vertices"]
     if simplify:
         small = simplify_mesh(mesh, factor=simplify, representative=representative)
         mesh.update(vertices=small["vertices"], faces=small["faces"], source=small["source"], simplify=small["report"])
@@ -457,6 +474,102 @@ def simplify_mesh(mesh, cell=None, factor=None, origin=None, dims=None, represen
             else:
                 raise ValueError("simplify_mesh: 'vertices_utm' under representative='mean' has to be computed again from the new vertices, and only a dict of "
                                  "extract_mesh knows its scene transform; drop the key, or use representative='nearest'")
+    return out
+
+
+SMOOTH_ONE = 1 << 16                 # quanta per unit (EONERF_SMOOTH_FRAC_BITS)
+SMOOTH_MAX_STEPS = 4096
+SMOOTH_STATUS_CLAMPED = 1
+SMOOTH_COUNTS = ("free", "open", "pinned", "no_corner", "not_quantisable", "dead_faces")
+
+
+def _factor_q(value, what):
+    value = float(value)
+    if not abs(value) <= 1.0:
+        raise ValueError(f"{what}={value!r}: a factor in [-1, 1]")
+    return int(np.rint(np.float64(value) * SMOOTH_ONE))           # llrint: ties to even
+
+
+@torch.no_grad()
+def smooth_mesh(mesh, iterations=10, lam=0.5, mu=-0.53, origin=None, unit=None, pinned=None, pin_open=True):
+    """The mesh after `iterations` lambda|mu iterations of Taubin smoothing, by the rule of csrc/eonerf_smooth.h: per iteration a step
+    of the face-weighted umbrella operator with factor lam, then one with factor mu (mu=None or 0: plain Laplacian, one step an
+    iteration).  Positions are integers of 2^-16 unit on the grid (origin, unit), every sum is an integer sum: the result does not
+    depend on the order of the faces or of the device's lanes.  Every vertex, every face and their order are kept.
+    mesh: a dict of extract_mesh / simplify_mesh, or a (vertices, faces) pair, on the GPU.
+    The grid: a dict that knows its lattice gives origin and unit (the lattice origin and spacing); otherwise unit= is one number or
+    three, and the defaults cost one more read-back: origin the lower corner of the finite vertices' bounding box, unit its largest
+    extent / 4096 on all axes.  A vertex further than 8192 units from the origin, or not finite, stays as it is and its faces count for
+    nothing.
+    pinned: a mask [V] (bool or bytes) of vertices that keep their bits.  pin_open: vertices on an open boundary keep theirs too.
+    Returns a MeshDict: the same "faces" tensor, new "vertices", every other key of an input dict carried over ("vertices_utm" computed
+    again from the new vertices: a dict of extract_mesh knows its scene transform), and "report": the counts ("free", "open", "pinned"
+    by the mask, "no_corner", "not_quantisable", "dead_faces"), the grid ("origin", "unit"), "steps" (the factors in 2^-16), "iterations"
+    and "clamped" (a step wanted to leave the 8192 units and was held).  iterations=0: no library call, the same bits.
+    One host synchronisation: the read-back of the counts and the status."""
+    vertices, faces = _mesh_arrays(mesh)
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f"iterations={iterations}: not negative")
+    pair = [_factor_q(lam, "lam")] + ([_factor_q(mu, "mu")] if mu else [])
+    steps = pair * iterations
+    if len(steps) > SMOOTH_MAX_STEPS:
+        raise ValueError(f"iterations={iterations}: {len(steps)} steps, and one call takes {SMOOTH_MAX_STEPS}")
+    dev = vertices.device
+    n_v, n_t = vertices.shape[0], faces.shape[0]
+    lattice = getattr(mesh, "lattice", None)
+    if unit is None and lattice is not None:
+        unit = lattice["spacing"]
+        if origin is None:
+            origin = lattice["origin"]
+    if unit is not None:
+        unit = _triple(unit, "unit")
+        if not all(math.isfinite(u) and u > 0 for u in unit):
+            raise ValueError(f"unit={tuple(unit)!r}: every unit must be finite and positive")
+    if pinned is not None:
+        pinned = torch.as_tensor(pinned).to(dev).reshape(-1).ne(0).to(torch.uint8).contiguous()
+        if pinned.shape[0] != n_v:
+            raise ValueError(f"pinned: a mask of {n_v} vertices, not {pinned.shape[0]}")
+    out = MeshDict(mesh) if isinstance(mesh, dict) else MeshDict({"vertices": vertices, "faces": faces})
+    if isinstance(mesh, dict):
+        out.lattice, out.scene = lattice, getattr(mesh, "scene", None)
+    if not steps:
+        return out
+    if out.get("vertices_utm") is not None and out.scene is None:
+        raise ValueError("smooth_mesh: 'vertices_utm' has to be computed again from the new vertices, and only a dict of extract_mesh knows its scene "
+                         "transform; drop the key")
+    if origin is None or unit is None:                      # the bounding box of the finite vertices: one more read-back
+        finite = vertices[torch.isfinite(vertices).all(dim=1)]
+        lo = finite.min(dim=0).values.tolist() if finite.shape[0] else [0.0, 0.0, 0.0]
+        hi = finite.max(dim=0).values.tolist() if finite.shape[0] else lo
+        if origin is None:
+            origin = lo
+        if unit is None:
+            extent = max(h - l for h, l in zip(hi, lo))
+            unit = [extent / 4096.0 if extent > 0 else 1.0] * 3
+    origin, unit = _f3(_triple(origin, "origin"), "origin"), _f3(unit, "unit")
+    if not all(u > 0 for u in unit):
+        raise ValueError(f"unit={tuple(unit)!r}: every unit must be positive in fp32")
+    L = _lib.lib()
+    nb = L.eonerf_smooth_workspace_bytes(n_v, n_t)
+    if not nb:
+        raise ValueError(f"{n_v} vertices and {n_t} faces: one call takes 2^31 - 1 vertices and 2^29 faces")
+    v_in = vertices if n_v else torch.zeros(1, 3, dtype=torch.float32, device=dev)          # the library takes no null pointer
+    f_in = faces if n_t else torch.zeros(1, 3, dtype=torch.int32, device=dev)
+    lam_q = (C.c_int32 * len(steps))(*steps)
+    with torch.cuda.device(dev):
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        back = torch.zeros(7, dtype=torch.int64, device=dev)           # the six counts and, in the low half of the seventh, the status word
+        moved = torch.empty(max(n_v, 1), 3, dtype=torch.float32, device=dev)
+        _lib.check(L.eonerf_smooth_build(_ptr(v_in), n_v, _ptr(f_in), n_t, origin, unit, _ptr(pinned), int(bool(pin_open)), _ptr(ws), nb, _ptr(back), _stream()))
+        _lib.check(L.eonerf_smooth_run(_ptr(v_in), n_v, n_t, origin, unit, lam_q, len(steps), _ptr(ws), nb, _ptr(moved), C.c_void_p(back.data_ptr() + 48), _stream()))
+        numbers = back.tolist()                                        # the host synchronisation
+    out["vertices"] = moved[:n_v]
+    out["faces"] = mesh["faces"] if isinstance(mesh, dict) else faces
+    out["report"] = dict(zip(SMOOTH_COUNTS, numbers[:6]), vertices=n_v, faces=n_t, origin=tuple(origin), unit=tuple(unit), steps=list(steps), iterations=iterations,
+                         lam=float(lam), mu=float(mu) if mu else 0.0, pin_open=bool(pin_open), clamped=bool(numbers[6] & SMOOTH_STATUS_CLAMPED))
+    if out.get("vertices_utm") is not None:
+        out["vertices_utm"] = out["vertices"].double() * out.scene[0] + out.scene[1]
     return out
 
 

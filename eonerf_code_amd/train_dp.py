@@ -42,8 +42,13 @@ a guess that has not been measured on a converged scene.  `--mesh_min_component 
 with any of them the PLY also carries each vertex' component id.  `--mesh_simplify K` (with `--mesh_representative mean|nearest`,
 default mean) clusters the mesh's vertices on cells of K lattice spacings before normals and albedo are taken (mesh.simplify_mesh); the
 status line then also shows the counts before, `vertices_in=` and `faces_in=`.  It is off by default -- what it costs in DSM MAE on a
-converged scene has not been measured -- and acts only together with `--mesh_out`.  Together with `--gt_dsm` rank 0 then rasterises
-the mesh it saved (filtered, simplified) straight from above on the lidar DSM's grid, registers it and prints `mesh/mae=` once
+converged scene has not been measured -- and acts only together with `--mesh_out`.  `--mesh_smooth K` (with `--mesh_smooth_lambda L`
+and `--mesh_smooth_mu M`, defaults 0.5 and -0.53) runs K lambda|mu iterations of Taubin smoothing in units of one lattice spacing on
+the extracted mesh, before the simplification, the normals and the albedo (mesh.smooth_mesh); it moves vertices and keeps every vertex
+and face, vertices on an open boundary stay put, and the status line then ends in `smooth=K | open=N`, N the open vertices.  It is off
+by default -- what it does to the DSM MAE is a measurement in profiles/smooth_ab.txt, not a default -- and acts only together with
+`--mesh_out`.  Together with `--gt_dsm` rank 0 then rasterises
+the mesh it saved (filtered, smoothed, simplified) straight from above on the lidar DSM's grid, registers it and prints `mesh/mae=` once
 (eonerf_code_amd.mesh.evaluate_mesh_dsm): the mesh on the scale of val/mae.  Without the flag nothing changes.
 """
 import argparse
@@ -100,6 +105,9 @@ def main():
     ap.add_argument("--mesh_keep_largest", type=int, default=0, help="keep the K largest solids of the mesh, ties included (0: keep all; only with --mesh_out)")
     ap.add_argument("--mesh_fill_cavities", action="store_true", help="drop closed inner surfaces from the mesh (only with --mesh_out)")
     ap.add_argument("--mesh_simplify", type=int, default=0, help="cluster the mesh's vertices on cells of K lattice spacings (0: off; only with --mesh_out)")
+    ap.add_argument("--mesh_smooth", type=int, default=0, help="lambda|mu iterations of Taubin smoothing on the extracted mesh (0: off; only with --mesh_out)")
+    ap.add_argument("--mesh_smooth_lambda", type=float, default=0.5, help="the positive factor of a smoothing iteration")
+    ap.add_argument("--mesh_smooth_mu", type=float, default=-0.53, help="the negative factor of a smoothing iteration (0: plain Laplacian)")
     ap.add_argument("--mesh_representative", choices=["mean", "nearest"], default="mean", help="a cell's vertex: the mean of its vertices, or the one nearest to it")
     ap.add_argument("--rpc_correction", action="store_true", help="learn a 3-D offset per image, added to that image's ray origins (opt.py:80); single process only")
     ap.add_argument("--rpc_lr", type=float, default=None, help="learning rate of the offsets (default: --lr)")
@@ -250,12 +258,14 @@ def main():
                     cleaned = bool(args.mesh_min_component or args.mesh_keep_largest or args.mesh_fill_cavities)
                     mesh = extract_mesh(field, resolution=args.mesh_res, level=args.mesh_level, min_component_points=args.mesh_min_component,
                                         keep_largest=args.mesh_keep_largest, fill_cavities=args.mesh_fill_cavities, components=cleaned,
-                                        simplify=args.mesh_simplify, representative=args.mesh_representative)
+                                        simplify=args.mesh_simplify, representative=args.mesh_representative, smooth=args.mesh_smooth,
+                                        smooth_lambda=args.mesh_smooth_lambda, smooth_mu=args.mesh_smooth_mu)
                     os.makedirs(os.path.dirname(os.path.abspath(args.mesh_out)), exist_ok=True)
                     save_ply(args.mesh_out, mesh)
                     print(f"step={step} | mesh={args.mesh_out} | vertices={mesh['vertices'].shape[0]} | faces={mesh['faces'].shape[0]} | "
                           f"level={mesh['level']:.6g}" +
-                          (f" | vertices_in={mesh['simplify']['vertices_in']} | faces_in={mesh['simplify']['faces_in']}" if args.mesh_simplify else ""), flush=True)
+                          (f" | vertices_in={mesh['simplify']['vertices_in']} | faces_in={mesh['simplify']['faces_in']}" if args.mesh_simplify else "") +
+                          (f" | smooth={args.mesh_smooth} | open={mesh['smooth']['open']}" if args.mesh_smooth else ""), flush=True)
                     if cleaned:
                         sizes = mesh["component_points"]
                         print(f"step={step} | mesh_components={int(torch.unique(mesh['component']).numel())} | "
