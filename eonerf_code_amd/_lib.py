@@ -204,6 +204,19 @@ API_STAGED_SMOOTH = {
         "eonerf_smooth_run": (i, [vp, i64, i64, f3, f3, i32p, i, vp, sz, vp, vp, vp]),
     },
 }
+# Likewise a table of its own (the two staged ABI tests pin the tables above); tests/test_raycast_abi_cpu.py holds it to the header.
+# lib() binds it after API_STAGED_SMOOTH.
+API_STAGED_RAYCAST = {
+    # rays against a mesh through a uniform grid (mesh.MeshRaycaster, mesh.render_mesh, mesh.vertex_visibility)
+    "eonerf_raycast.h": {
+        "eonerf_raycast_version": (i, []),
+        "eonerf_raycast_workspace_bytes": (sz, [i3, i64, i64]),
+        "eonerf_raycast_count": (i, [vp, i64, vp, i64, d3, d3, i3, vp, vp, vp]),
+        "eonerf_raycast_build": (i, [vp, i64, vp, i64, d3, d3, i3, vp, i64, vp, sz, vp]),
+        "eonerf_raycast_closest": (i, [vp, i64, vp, i64, d3, d3, i3, i64, vp, sz, vp, i64, vp, i64, i64, d, d, vp, vp, vp, vp, vp]),
+        "eonerf_raycast_occluded": (i, [vp, i64, vp, i64, d3, d3, i3, i64, vp, sz, vp, i64, vp, i64, i64, d, d, vp, vp, vp, vp]),
+    },
+}
 
 
 def build(verbose=False):
@@ -255,7 +268,7 @@ def lib():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the EO-NeRF hot path has no non-HIP fallback)")
     L = C.CDLL(LIB_PATH)
-    for group in list(API.values()) + list(API_STAGED.values()) + list(API_STAGED_SMOOTH.values()):
+    for group in list(API.values()) + list(API_STAGED.values()) + list(API_STAGED_SMOOTH.values()) + list(API_STAGED_RAYCAST.values()):
         for name, (restype, argtypes) in group.items():
             fn = getattr(L, name)               # resolves the symbol: a missing one fails here, at load
             fn.restype, fn.argtypes = restype, argtypes

@@ -30,7 +30,14 @@ pin_open=False.  Every sum is an integer sum: a pure, bit-reproducible function 
 after the extraction and in front of simplify, normals and albedo.  Off by default: what it does to the DSM MAE of a trained field is
 in profiles/smooth_ab.txt, not in a default.
 
-Not here: cotangent or area weights, bilateral or feature-preserving filters, implicit smoothing, re-projection onto the level set,
+MeshRaycaster, render_mesh and vertex_visibility (csrc/eonerf_raycast.h, a staged header) cast rays against a mesh: the closest hit
+(t, face, barycentric weights) or whether anything blocks a ray, defined as the minimum over ALL triangles by a rule in fp64 and found
+through a uniform grid that may not change a bit of it.  render_mesh gives the depth of a mesh through the camera of an input image on
+the scale of render_image's depth, per-vertex tables interpolated there, and the hard shadow of that image's sun; vertex_visibility says
+which vertices a sun or a satellite sees.  The default grid and both bias defaults are guesses (profiles/raycast_ab.txt has what was measured).
+
+Not here: a BVH or any structure for meshes that do not fit a uniform grid, perspective cameras other than ray tables, anti-aliasing, texture atlases, a loss on the
+mesh's shadows, cotangent or area weights, bilateral or feature-preserving filters, implicit smoothing, re-projection onto the level set,
 sliding open vertices along their boundary, marching cubes, vertex refinement along the gradient, filters on area or height above ground, labelling of the mesh graph
 itself, edge collapse, quadric error representatives, welding by distance, removal of duplicate triangles, textures, skipping empty space through the occupancy grid while the volume is filled, volumes larger
 than one call, OBJ / glTF writers.
@@ -650,6 +657,246 @@ def evaluate_mesh_dsm(mesh, gt, roi, scene_offset, scene_scale, water=None, scal
     if not return_all:
         return out
     return {"mae": out[0], "err": out[1], "dsm": dsm, "transform": transform}
+
+
+RAYCAST_MAX_DIM = 4096              # EONERF_RAYCAST_MAX_DIM
+RAYCAST_MAX_CELLS = 1 << 27
+RAYCAST_DEFAULT_DIM = 256           # cells per axis at most by default: the fastest of 32 .. 256 on the one scene measured (profiles/raycast_ab.txt)
+RAYCAST_BIAS_SPACINGS = 1.0 / 64    # the default shadow / visibility bias in lattice spacings: a guess, not measured
+
+
+def _ray_columns(a, what):
+    """An fp32 [N, 3] view whose rows are contiguous (columns of a ray table are read in place) -> (tensor, row stride in floats)."""
+    if a.dim() != 2 or a.shape[1] != 3:
+        raise ValueError(f"{what}: [N, 3], not {tuple(a.shape)}")
+    if a.dtype != torch.float32 or (a.shape[0] > 1 and a.stride(0) < 3) or a.stride(1) != 1:
+        a = a.detach().float().contiguous()
+    return a, (int(a.stride(0)) if a.shape[0] > 1 else 3)
+
+
+class MeshRaycaster:
+    """A mesh with the uniform grid of csrc/eonerf_raycast.h built over it: one build, any number of casts.  Every answer is the one a
+    brute force over all triangles gives by the header's rule, bit for bit; the grid only makes it cheap.
+    mesh: a dict of extract_mesh / simplify_mesh / smooth_mesh, or a (vertices, faces) pair, on the GPU.
+    bounds: ((x0, y0, z0), (x1, y1, z1)), the box of the grid.  Default: the lattice a dict of extract_mesh came from, grown by half a
+    spacing; otherwise the extent of the finite vertices (one read-back), grown by 2^-10 of its largest side.  A triangle with a vertex
+    outside the box, a vertex that is not finite or an index outside the mesh is dropped: counted, never hit.
+    dims: cells per axis, one int or (nx, ny, nz); at most 4096 each and 2^27 in all.  The default -- min(RAYCAST_DEFAULT_DIM,
+    ceil(sqrt(faces / 2))) on every axis, a surface of T faces crossing about sqrt(T / 2) cells a side -- is a guess until it has been
+    measured on a converged scene: RAYCAST_DEFAULT_DIM = 256 is the fastest of 32, 64, 128 and 256 for a 512 x 512 view of the 256^3
+    extraction of a 2,000-step synthetic field (profiles/raycast_ab.txt), the only scene measured; the square-root rule is not measured at all.
+    One host synchronisation at construction: the read-back of the number of list entries."""
+
+    def __init__(self, mesh, dims=None, bounds=None):
+        self.vertices, self.faces = _mesh_arrays(mesh)
+        dev = self.vertices.device
+        self.n_v, self.n_t = self.vertices.shape[0], self.faces.shape[0]
+        self.lattice = getattr(mesh, "lattice", None)
+        if bounds is None and self.lattice is not None:
+            o, s, (nz, ny, nx) = self.lattice["origin"], self.lattice["spacing"], self.lattice["shape"]
+            ends = [(float(o[c]), float(o[c]) + float(s[c]) * (n - 1)) for c, n in enumerate((nx, ny, nz))]
+            bounds = ([min(a, b) - 0.5 * abs(float(s[c])) for c, (a, b) in enumerate(ends)], [max(a, b) + 0.5 * abs(float(s[c])) for c, (a, b) in enumerate(ends)])
+        if bounds is None:
+            finite = self.vertices[torch.isfinite(self.vertices).all(dim=1)]
+            lo = finite.min(dim=0).values.double().tolist() if finite.shape[0] else [0.0, 0.0, 0.0]
+            hi = finite.max(dim=0).values.double().tolist() if finite.shape[0] else lo
+            grow = max(h - l for h, l in zip(hi, lo)) * 2.0 ** -10 or 1.0
+            bounds = ([l - grow for l in lo], [h + grow for h in hi])
+        lo, hi = _triple(bounds[0], "bounds[0]"), _triple(bounds[1], "bounds[1]")
+        if not all(math.isfinite(l) and math.isfinite(h) and l < h for l, h in zip(lo, hi)):
+            raise ValueError(f"bounds={bounds!r}: finite, with lo < hi on every axis")
+        if dims is None:
+            dims = min(RAYCAST_DEFAULT_DIM, max(1, math.ceil(math.sqrt(self.n_t / 2.0))))
+        dims = [int(dims)] * 3 if isinstance(dims, int) else [int(n) for n in dims]
+        if len(dims) != 3 or not all(1 <= n <= RAYCAST_MAX_DIM for n in dims) or dims[0] * dims[1] * dims[2] > RAYCAST_MAX_CELLS:
+            raise ValueError(f"dims={dims!r}: three entries of 1 .. {RAYCAST_MAX_DIM} and at most 2^27 cells")
+        self.bounds, self.dims = (tuple(lo), tuple(hi)), tuple(dims)
+        self._lo, self._hi, self._dims = (C.c_double * 3)(*lo), (C.c_double * 3)(*hi), (C.c_int * 3)(*dims)
+        L = _lib.lib()
+        self._v = self.vertices if self.n_v else torch.zeros(1, 3, dtype=torch.float32, device=dev)       # the library takes no null pointer
+        self._f = self.faces if self.n_t else torch.zeros(1, 3, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            cell_counts = torch.empty(dims[0] * dims[1] * dims[2], dtype=torch.int32, device=dev)
+            self._built = torch.zeros(2, dtype=torch.int64, device=dev)
+            _lib.check(L.eonerf_raycast_count(_ptr(self._v), self.n_v, _ptr(self._f), self.n_t, self._lo, self._hi, self._dims, _ptr(cell_counts), _ptr(self._built), _stream()))
+            self.entries, self.dropped = self._built.tolist()               # the host synchronisation
+            nb = L.eonerf_raycast_workspace_bytes(self._dims, self.n_t, self.entries)
+            if not nb:
+                raise ValueError(f"{self.entries} list entries: one grid takes 2^31 - 1; use fewer cells")
+            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            _lib.check(L.eonerf_raycast_build(_ptr(self._v), self.n_v, _ptr(self._f), self.n_t, self._lo, self._hi, self._dims, _ptr(cell_counts), self.entries, _ptr(self._ws),
+                                              nb, _stream()))
+        self._cast = torch.zeros(2, 3, dtype=torch.int64, device=dev)       # the counters of the last closest / occluded call
+
+    def _args(self, origins, dirs, t_min, t_max):
+        o, so = _ray_columns(origins, "origins")
+        d, sd = _ray_columns(dirs, "dirs")
+        if o.shape[0] != d.shape[0] or o.device != self.vertices.device or d.device != o.device:
+            raise ValueError("origins and dirs: one row per ray, on the mesh's device")
+        t_min, t_max = float(t_min), float(t_max)
+        if not (0.0 <= t_min <= t_max and math.isfinite(t_min)):
+            raise ValueError(f"t_min={t_min!r}, t_max={t_max!r}: need 0 <= t_min <= t_max")
+        head = (_ptr(self._v), self.n_v, _ptr(self._f), self.n_t, self._lo, self._hi, self._dims, self.entries, _ptr(self._ws), self._ws.numel())
+        return o, d, head + (_ptr(o), so, _ptr(d), sd, o.shape[0], t_min, t_max)
+
+    @torch.no_grad()
+    def closest(self, origins, dirs, t_min=0.0, t_max=float("inf")):
+        """The first triangle each ray o + t d meets with t_min <= t <= t_max (d is not normalised: t is in its units).  origins, dirs:
+        fp32 [N, 3] on the GPU; columns of a wider table are read in place.  Returns {"t": fp64 [N], NaN on a miss; "face": int32 [N],
+        rows of the mesh's faces, -1; "bary": fp32 [N, 3], the weights of the face's three corners, NaN; "hit": bool [N]}.  Nothing is
+        read back."""
+        o, d, args = self._args(origins, dirs, t_min, t_max)
+        n, dev = o.shape[0], o.device
+        t = torch.empty(n, dtype=torch.float64, device=dev)
+        face = torch.empty(n, dtype=torch.int32, device=dev)
+        bary = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().eonerf_raycast_closest(*args, _ptr(t), _ptr(face), _ptr(bary), _ptr(self._cast[0]), _stream()))
+        return {"t": t, "face": face, "bary": bary, "hit": face >= 0}
+
+    @torch.no_grad()
+    def occluded(self, origins, dirs, skip_face=None, t_min=0.0, t_max=float("inf")):
+        """bool [N]: whether any triangle but skip_face[r] (int32 [N], or None) meets ray r with t_min <= t <= t_max."""
+        o, d, args = self._args(origins, dirs, t_min, t_max)
+        n, dev = o.shape[0], o.device
+        if skip_face is not None:
+            skip_face = skip_face.to(dev, torch.int32).reshape(-1).contiguous()
+            if skip_face.shape[0] != n:
+                raise ValueError(f"skip_face: one face per ray ({n}), not {skip_face.shape[0]}")
+        out = torch.empty(n, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().eonerf_raycast_occluded(*args, _ptr(skip_face), _ptr(out), _ptr(self._cast[1]), _stream()))
+        return out.bool()
+
+    def counts(self):
+        """The counters as ints (one host synchronisation): the grid's "entries", "dropped" triangles, "faces", "dims"; of the last
+        closest() call "cast", "rejected", "hits"; of the last occluded() call "shadow_cast", "shadow_rejected", "shadow_hits"."""
+        near, block = self._cast.tolist()
+        return dict(entries=self.entries, dropped=self.dropped, faces=self.n_t, dims=self.dims, cast=near[0], rejected=near[1], hits=near[2], shadow_cast=block[0],
+                    shadow_rejected=block[1], shadow_hits=block[2])
+
+    def default_bias(self):
+        """RAYCAST_BIAS_SPACINGS of the smallest lattice spacing (without a lattice: of the smallest cell side).  A guess: far above the
+        rounding of a hit point in fp32 for a scene in the unit cube, far below anything a mesh of that lattice resolves."""
+        if self.lattice is not None:
+            return RAYCAST_BIAS_SPACINGS * min(abs(float(s)) for s in self.lattice["spacing"])
+        return RAYCAST_BIAS_SPACINGS * min((h - l) / n for l, h, n in zip(*self.bounds, self.dims))
+
+
+def _table_of(rays):
+    """The fp32 [N, 11] ray table of a SatRays or of a table."""
+    if isinstance(rays, torch.Tensor):
+        table = rays
+    else:
+        from .datasets.satellite import namedtuple_map, satrays_to_table
+        if rays.origins.dim() == 3:
+            rays = namedtuple_map(lambda r: r.reshape([-1] + list(r.shape[2:])), rays)
+        table = satrays_to_table(rays)[0]
+    if table.dim() != 2 or table.shape[1] < 6 or not table.is_cuda:
+        raise ValueError("rays: a SatRays or an fp32 table [N, >= 6] on the GPU")
+    return table.detach().float().contiguous()
+
+
+@torch.no_grad()
+def render_mesh(mesh, rays, attributes=("albedo", "normals"), shadows=True, shadow_bias=None, raycaster=None):
+    """The mesh seen along the rays of a view, by the rule of csrc/eonerf_raycast.h.
+    rays: a ray table [N, 11] (origins 0..2, directions 3..5, sun 8..10) or a SatRays, as render_image takes.
+    Returns a dict: "depth" fp32 [N, 1], the ray parameter of the first surface -- the scale of render_image's "depth", so it goes into
+    get_utmalt_from_nerf_prediction unchanged -- NaN on a miss; "hit" bool [N]; "face" int32 [N] (-1); "bary" fp32 [N, 3]; per name in
+    `attributes` that the mesh dict carries, the per-vertex table interpolated with bary, fp32 [N, C], NaN on a miss.
+    shadows: also "sun_visible" fp32 [N, 1]: 1 where the ray from the hit point towards the sun is free, 0 where the mesh blocks it,
+    NaN on a miss.  Columns 8..10 hold the direction the sun's light travels (datasets.satellite.sun_direction: downwards), so the ray
+    runs along their negation, as the field's own shadow pass does.  It starts at the hit point o + t d formed in fp64 and rounded once
+    to fp32, skips the face it starts on and begins at t = shadow_bias (in units of the sun column: a unit vector of the scene for a
+    dataset's table).  shadow_bias defaults to MeshRaycaster.default_bias(), 1/64 of a lattice spacing: a guess, not measured -- too small and a
+    neighbouring face of a concave corner shades its own edge through fp32 rounding, too large and contact shadows thinner than it vanish.
+    raycaster: a MeshRaycaster of this mesh to reuse; otherwise one is built (and returned under "raycaster")."""
+    caster = raycaster if raycaster is not None else MeshRaycaster(mesh)
+    table = _table_of(rays)
+    o, d = table[:, 0:3], table[:, 3:6]
+    near = caster.closest(o, d)
+    hit, face, bary = near["hit"], near["face"], near["bary"]
+    out = {"depth": near["t"].float().reshape(-1, 1), "hit": hit, "face": face, "bary": bary, "raycaster": caster}
+    if isinstance(mesh, dict) and attributes:
+        corners = caster.faces[face.clamp(min=0).long()].long()                        # [N, 3] vertex ids; face 0 stands in on a miss
+        for name in attributes:
+            a = mesh.get(name)
+            if a is None:
+                continue
+            a = a.detach().to(table.device, torch.float32)
+            a = a.reshape(a.shape[0], -1)
+            if a.shape[0] != caster.n_v:
+                raise ValueError(f"mesh[{name!r}]: a per-vertex table of {caster.n_v} rows, not {a.shape[0]}")
+            if caster.n_t == 0:
+                out[name] = torch.full((table.shape[0], a.shape[1]), float("nan"), device=table.device)
+                continue
+            value = (a[corners] * bary.unsqueeze(-1)).sum(dim=1)
+            out[name] = torch.where(hit.unsqueeze(-1), value, torch.full_like(value, float("nan")))
+    if shadows:
+        if table.shape[1] < 11:
+            raise ValueError("shadows=True reads the sun direction from columns 8..10 of the ray table")
+        bias = caster.default_bias() if shadow_bias is None else float(shadow_bias)
+        point = (o.double() + near["t"].unsqueeze(-1) * d.double()).float()            # NaN on a miss: that ray is rejected
+        blocked = caster.occluded(point, -table[:, 8:11], skip_face=face, t_min=bias)
+        nan = torch.full((table.shape[0],), float("nan"), device=table.device)
+        out["sun_visible"] = torch.where(hit, (~blocked).float(), nan).reshape(-1, 1)
+        out["shadow_bias"] = bias
+    return out
+
+
+@torch.no_grad()
+def vertex_visibility(mesh, directions, bias=None, raycaster=None):
+    """bool [V, K]: whether vertex v sees the sun or the satellite k -- the ray v - t directions[k], t >= bias, meets no triangle.
+    directions: fp32 [K, 3] as a ray table holds them, pointing from the sun or the satellite TOWARDS the scene: a relight.sun_table, or
+    the view directions of the satellites (columns 3..5 of a row of each image).  A vertex that is not finite sees nothing.  bias (default MeshRaycaster.default_bias(), a guess) keeps the ray off the faces that
+    share the vertex: they all meet it at t = 0.  Visibility for colouring a mesh from the images, sun hours, a sky-view factor."""
+    caster = raycaster if raycaster is not None else MeshRaycaster(mesh)
+    directions = torch.as_tensor(directions, dtype=torch.float32, device=caster.vertices.device).reshape(-1, 3)
+    bias = caster.default_bias() if bias is None else float(bias)
+    finite = torch.isfinite(caster.vertices).all(dim=1)
+    out = torch.zeros(caster.n_v, directions.shape[0], dtype=torch.bool, device=caster.vertices.device)
+    if caster.n_v == 0:
+        return out
+    for k in range(directions.shape[0]):
+        d = (-directions[k]).expand(caster.n_v, 3).contiguous()
+        out[:, k] = finite & ~caster.occluded(caster.vertices, d, t_min=bias)
+    return out
+
+
+@torch.no_grad()
+def mesh_view_metrics(field, mesh, images, chunk=5120, render_step_size=None, occupancy_grid=None, raycaster=None, shadow_bias=None):
+    """A mesh judged through the cameras of held-out images: device double[4] = the mean |mesh depth - field depth| over the rays that
+    hit the mesh (ray parameters: the scale of render_image's "depth"), the number of those rays, the share of them where the mesh's
+    hard shadow agrees with the field's learned one (sun_visible == (geo_shadows >= 0.5)), the number of rays cast.
+    images: dicts with "rays" [h * w, 11], as validation.validate_images takes.  The field depth comes from a depth-only export render
+    of the same rays, geo_shadows from a full export render with the shadow pass on (epoch 2).  Nothing is read back beyond
+    render_image's own sample count."""
+    from .datasets.satellite import define_satrays_from_tensors
+    from .sat_rendering import render_image
+    from .validation import _step_size_of
+    if render_step_size is None:
+        render_step_size = _step_size_of(field)
+    caster = raycaster if raycaster is not None else MeshRaycaster(mesh)
+    dev = caster.vertices.device
+    sums = torch.zeros(4, dtype=torch.float64, device=dev)
+    was_training = field.training
+    field.eval()
+    try:
+        for data in images:
+            rays = data["rays"].to(dev, torch.float32).contiguous()
+            sat = define_satrays_from_tensors(rays, torch.zeros(rays.shape[0], 1, dtype=torch.int64, device=dev))
+            seen = render_mesh(mesh, rays, attributes=(), shadows=True, shadow_bias=shadow_bias, raycaster=caster)
+            depth = render_image(field, occupancy_grid, sat, None, None, chunk=chunk, render_step_size=render_step_size, only_depth=True, eval=True)[0]["depth"]
+            full = render_image(field, occupancy_grid, sat, None, None, epoch_idx=2, chunk=chunk, render_step_size=render_step_size, eval=True)[0]
+            hit = seen["hit"]
+            diff = (seen["depth"].reshape(-1).double() - depth.reshape(-1).double()).abs()
+            agree = (seen["sun_visible"].reshape(-1) >= 0.5) == (full["geo_shadows"].reshape(-1) >= 0.5)
+            sums += torch.stack([torch.where(hit, diff, torch.zeros_like(diff)).sum(), hit.sum().double(), (agree & hit).sum().double(),
+                                 torch.tensor(float(rays.shape[0]), dtype=torch.float64, device=dev)])
+    finally:
+        field.train(was_training)
+    n = sums[1].clamp(min=1.0)
+    return torch.stack([sums[0] / n, sums[1], sums[2] / n, sums[3]])
 
 
 def _host(a):

@@ -50,6 +50,10 @@ by default -- what it does to the DSM MAE is a measurement in profiles/smooth_ab
 `--mesh_out`.  Together with `--gt_dsm` rank 0 then rasterises
 the mesh it saved (filtered, smoothed, simplified) straight from above on the lidar DSM's grid, registers it and prints `mesh/mae=` once
 (eonerf_code_amd.mesh.evaluate_mesh_dsm): the mesh on the scale of val/mae.  Without the flag nothing changes.
+`--mesh_views` (with `--mesh_out` and `--val_images`; refused without them) casts the rays of every held-out image against the saved
+mesh on rank 0 (eonerf_code_amd.mesh.mesh_view_metrics) and prints `mesh/view_depth=`, the mean |mesh depth - field depth| over the rays
+that hit, the field depth from a depth-only export render of the same rays; `mesh/view_hits=`; and `mesh/shadow_agree=`, the share of
+hit rays where the mesh's hard shadow for the image's sun equals geo_shadows >= 0.5.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -108,11 +112,15 @@ def main():
     ap.add_argument("--mesh_smooth", type=int, default=0, help="lambda|mu iterations of Taubin smoothing on the extracted mesh (0: off; only with --mesh_out)")
     ap.add_argument("--mesh_smooth_lambda", type=float, default=0.5, help="the positive factor of a smoothing iteration")
     ap.add_argument("--mesh_smooth_mu", type=float, default=-0.53, help="the negative factor of a smoothing iteration (0: plain Laplacian)")
+    ap.add_argument("--mesh_views", action="store_true",
+                    help="cast every --val_images view's rays against the saved mesh: depth against the field's, hits, shadow agreement (only with --mesh_out and --val_images)")
     ap.add_argument("--mesh_representative", choices=["mean", "nearest"], default="mean", help="a cell's vertex: the mean of its vertices, or the one nearest to it")
     ap.add_argument("--rpc_correction", action="store_true", help="learn a 3-D offset per image, added to that image's ray origins (opt.py:80); single process only")
     ap.add_argument("--rpc_lr", type=float, default=None, help="learning rate of the offsets (default: --lr)")
     ap.add_argument("--resume", default=None, help="checkpoint to continue from (weights, optimizer state and, with --rpc_correction, the offsets)")
     args = ap.parse_args()
+    if args.mesh_views and not (args.mesh_out and args.val_images):
+        raise SystemExit("--mesh_views: the views of --val_images are cast against the mesh of --mesh_out; give both")
 
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     # EONERF_DP_REHEARSAL=1 (tests on a one-GPU box, not a deployment mode): every rank on cuda:0, gloo instead of RCCL; run it with
@@ -276,6 +284,11 @@ def main():
                         mesh_mae, mesh_cells = evaluate_mesh_dsm(mesh, gt["dsm"], [float(x) for x in gt["roi"]], gt["scene_offset"],
                                                                  gt["scene_scale"], water=gt["water"]).tolist()
                         print(f"step={step} | mesh/mae={mesh_mae:.4f} | mesh/cells={int(mesh_cells)}", flush=True)
+                    if args.mesh_views and val_images:                      # the saved mesh through the cameras of the held-out images
+                        from .mesh import mesh_view_metrics
+                        view_depth, view_hits, shadow_agree, view_rays = mesh_view_metrics(field, mesh, val_images, chunk=args.val_chunk, occupancy_grid=occ).tolist()
+                        print(f"step={step} | mesh/view_depth={view_depth:.5f} | mesh/view_hits={int(view_hits)} | mesh/view_rays={int(view_rays)} | "
+                              f"mesh/shadow_agree={shadow_agree:.4f}", flush=True)
                 if args.dump_params:                                        # replica-equality checks of the tests
                     torch.save(field.flat_params().detach().cpu(), f"{args.dump_params}.rank{rank}")
                 if torch.distributed.is_initialized():
