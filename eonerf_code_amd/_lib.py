@@ -218,6 +218,20 @@ API_STAGED_RAYCAST = {
     },
 }
 
+# And a fourth (the three staged ABI tests pin the tables above); tests/test_texture_abi_cpu.py holds it to the header.  lib() binds it
+# after API_STAGED_RAYCAST.
+i64p = C.POINTER(i64)
+API_STAGED_TEXTURE = {
+    # the texture atlas of a mesh and the fused per-texel gather of the input images (texture.py)
+    "eonerf_texture.h": {
+        "eonerf_texture_version": (i, []),
+        "eonerf_texture_layout": (i, [i64, i, i64p]),
+        "eonerf_texture_uv": (i, [i64, i, vp, vp]),
+        "eonerf_texture_samples": (i, [vp, i64, vp, i64, i, i64, i64, f3, f3, i, i, vp, vp, vp, vp, vp, vp]),
+        "eonerf_texture_bake": (i, [vp, vp, i64, vp, vp, vp, i, i, vp, vp, vp, vp, fp, i, i, vp, vp, vp, vp, vp]),
+    },
+}
+
 
 def build(verbose=False):
     """Compile libeonerf_hip.so in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -268,7 +282,8 @@ def lib():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the EO-NeRF hot path has no non-HIP fallback)")
     L = C.CDLL(LIB_PATH)
-    for group in list(API.values()) + list(API_STAGED.values()) + list(API_STAGED_SMOOTH.values()) + list(API_STAGED_RAYCAST.values()):
+    for group in (list(API.values()) + list(API_STAGED.values()) + list(API_STAGED_SMOOTH.values()) + list(API_STAGED_RAYCAST.values())
+                  + list(API_STAGED_TEXTURE.values())):
         for name, (restype, argtypes) in group.items():
             fn = getattr(L, name)               # resolves the symbol: a missing one fails here, at load
             fn.restype, fn.argtypes = restype, argtypes

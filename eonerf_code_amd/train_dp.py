@@ -54,6 +54,11 @@ the mesh it saved (filtered, smoothed, simplified) straight from above on the li
 mesh on rank 0 (eonerf_code_amd.mesh.mesh_view_metrics) and prints `mesh/view_depth=`, the mean |mesh depth - field depth| over the rays
 that hit, the field depth from a depth-only export render of the same rays; `mesh/view_hits=`; and `mesh/shadow_agree=`, the share of
 hit rays where the mesh's hard shadow for the image's sun equals geo_shadows >= 0.5.  Without the flag nothing changes.
+`--mesh_texture FILE` (with `--mesh_out`; refused without it) is a torch file in the format of `--ortho` ("size" is not read).  After the
+mesh is saved, rank 0 bakes the images onto it (eonerf_code_amd.texture.bake_texture: a per-face atlas of `--mesh_texels` texels a leg,
+every texel projected through each image's RPC, occlusion against the mesh itself, median-fused) and writes <PATH stem>.obj, .mtl and
+.png beside the PLY (texture.save_obj); it prints `mesh/texels=`, the texels a face owns, and `mesh/textured=`, the share of them at
+least one image sees.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -114,6 +119,8 @@ def main():
     ap.add_argument("--mesh_smooth_mu", type=float, default=-0.53, help="the negative factor of a smoothing iteration (0: plain Laplacian)")
     ap.add_argument("--mesh_views", action="store_true",
                     help="cast every --val_images view's rays against the saved mesh: depth against the field's, hits, shadow agreement (only with --mesh_out and --val_images)")
+    ap.add_argument("--mesh_texture", default=None, help="torch file in the format of --ortho: bake the images onto the saved mesh, write <stem>.obj/.mtl/.png (only with --mesh_out)")
+    ap.add_argument("--mesh_texels", type=int, default=4, help="texels per triangle leg of the texture atlas (1 .. 64)")
     ap.add_argument("--mesh_representative", choices=["mean", "nearest"], default="mean", help="a cell's vertex: the mean of its vertices, or the one nearest to it")
     ap.add_argument("--rpc_correction", action="store_true", help="learn a 3-D offset per image, added to that image's ray origins (opt.py:80); single process only")
     ap.add_argument("--rpc_lr", type=float, default=None, help="learning rate of the offsets (default: --lr)")
@@ -121,6 +128,8 @@ def main():
     args = ap.parse_args()
     if args.mesh_views and not (args.mesh_out and args.val_images):
         raise SystemExit("--mesh_views: the views of --val_images are cast against the mesh of --mesh_out; give both")
+    if args.mesh_texture and not args.mesh_out:
+        raise SystemExit("--mesh_texture: the images are baked onto the mesh of --mesh_out; give both")
 
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     # EONERF_DP_REHEARSAL=1 (tests on a one-GPU box, not a deployment mode): every rank on cuda:0, gloo instead of RCCL; run it with
@@ -204,6 +213,12 @@ def main():
         for key in ("images", "rpcs", "size", "min_alt", "max_alt", "scene_offset", "scene_scale", "zone", "south"):
             if key not in ortho:
                 raise SystemExit(f"--ortho {args.ortho}: missing entry '{key}'")
+    mesh_texture = None
+    if args.mesh_texture:
+        mesh_texture = torch.load(args.mesh_texture, map_location="cpu")
+        for key in ("images", "rpcs", "min_alt", "max_alt", "scene_offset", "scene_scale", "zone", "south"):
+            if key not in mesh_texture:
+                raise SystemExit(f"--mesh_texture {args.mesh_texture}: missing entry '{key}'")
     pose_field = ""
     if args.resume:
         load_checkpoint(args.resume, field, trainer, occ_grid=occ)
@@ -289,6 +304,20 @@ def main():
                         view_depth, view_hits, shadow_agree, view_rays = mesh_view_metrics(field, mesh, val_images, chunk=args.val_chunk, occupancy_grid=occ).tolist()
                         print(f"step={step} | mesh/view_depth={view_depth:.5f} | mesh/view_hits={int(view_hits)} | mesh/view_rays={int(view_rays)} | "
                               f"mesh/shadow_agree={shadow_agree:.4f}", flush=True)
+                    if mesh_texture is not None:                            # the images on the saved mesh: <stem>.obj / .mtl / .png
+                        from .texture import bake_texture, save_obj
+                        mt = mesh_texture
+                        radiometric = len(mt["images"]) == args.n_images and mt["images"][0].shape[-1] == 3
+                        tex = bake_texture(mesh, mt["images"], mt["rpcs"], mt["scene_offset"], mt["scene_scale"], int(mt["zone"]), bool(mt["south"]),
+                                           float(mt["min_alt"]), float(mt["max_alt"]), texels=args.mesh_texels, field=field if radiometric else None)
+                        dev_v = mesh["vertices"].device
+                        mesh["vertices_utm"] = (mesh["vertices"].double() * torch.as_tensor(mt["scene_scale"], dtype=torch.float32).reshape(3).double().to(dev_v)
+                                                + torch.as_tensor(mt["scene_offset"], dtype=torch.float32).reshape(3).double().to(dev_v))
+                        obj = save_obj(os.path.splitext(args.mesh_out)[0] + ".obj", mesh, tex)[0]
+                        owned = tex["face"] >= 0
+                        n_owned = int(owned.sum())
+                        textured = int(((tex["count"] > 0) & owned).sum()) / max(n_owned, 1)
+                        print(f"step={step} | mesh_obj={obj} | mesh/texels={n_owned} | mesh/textured={textured:.4f}", flush=True)
                 if args.dump_params:                                        # replica-equality checks of the tests
                     torch.save(field.flat_params().detach().cpu(), f"{args.dump_params}.rank{rank}")
                 if torch.distributed.is_initialized():
