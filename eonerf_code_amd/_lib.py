@@ -177,6 +177,7 @@ API = {
     "eonerf_layout.h": {
         "eonerf_layout_version": (i, []),
         "eonerf_workspace_layout": (i, [vp, i, i, i, C.POINTER(u64), i]),
+        "eonerf_ray_layout": (i, [vp, i, i, C.POINTER(u64), i]),
     },
 }
 

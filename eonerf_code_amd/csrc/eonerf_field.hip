@@ -154,4 +154,9 @@ int eonerf_workspace_layout(const eonerf_ctx* ctx, int kind, int n, int flags, u
     return workspace_layout_table(carve_cfg(ctx), kind, n, flags, out, cap);
 }
 
+int eonerf_ray_layout(const eonerf_ctx* ctx, int n_rays, int flags, uint64_t* out, int cap) {
+    if (!ctx) return EONERF_E_ARG;
+    return ray_layout_table(carve_cfg(ctx), n_rays, flags, out, cap);
+}
+
 }  // extern "C"

@@ -1,4 +1,4 @@
-// The table behind eonerf_workspace_layout (include/eonerf_layout.h): plain host code, no HIP runtime calls -- shared by the entry point
+// The tables behind eonerf_workspace_layout and eonerf_ray_layout (include/eonerf_layout.h): plain host code, no HIP runtime calls -- shared by the entry points
 // (eonerf_field.hip) and the host-only test (tests/host/host_checks.cpp), which holds every entry to the carve's own pointers.
 // The offsets are read off the carve itself: carve_field_train / carve_render on a base that is never dereferenced, minus that base
 // (a null base is the carve's MEASURING mode and hands out null pointers only, so the base here is a fake non-null one, as in the host test).
@@ -31,4 +31,14 @@ inline int workspace_layout_table(const CarveCfg& cfg, int kind, int n, int flag
         layout_pass(w.sun, base, out + EONERF_LAYOUT_SUN);
     }
     return EONERF_LAYOUT_ENTRIES;
+}
+
+// The table behind eonerf_ray_layout: the per-ray buffers carve_render puts in front of the passes
+inline int ray_layout_table(const CarveCfg& cfg, int n_rays, int flags, uint64_t* out, int cap) {
+    if (!out || n_rays < 0 || cap < EONERF_RAY_ENTRIES) return EONERF_E_ARG;
+    uint8_t* base = reinterpret_cast<uint8_t*>((uintptr_t)1 << 40);
+    const RenderWs w = carve_render(cfg, base, n_rays, flags);
+    const void* m[EONERF_RAY_ENTRIES] = {w.cnt_first, w.cnt_retry, w.flags, w.ray_rec, w.g_ray, w.amb_save, w.det.rad_rays, w.det.emb_rays};
+    for (int k = 0; k < EONERF_RAY_ENTRIES; ++k) out[k] = m[k] ? (uint64_t)(reinterpret_cast<const uint8_t*>(m[k]) - base) : UINT64_MAX;
+    return EONERF_RAY_ENTRIES;
 }

@@ -20,6 +20,19 @@
  * Pass members, in the order of the carve: counts, offsets, n_pts (int); px, py, pz, tmid, delta, sigma, albedo [3][p_cap], ts, tb
  * (fp32 [p_cap]); simg (int [p_cap]); act, grd (the two slabs, bf16 or fp32 by the context's precision); masks; g_sigma, g_albedo
  * [3][p_cap], g_ts, g_tb, g_emb [p_cap][4], g_pos [3][p_cap] (fp32).
+ *
+ * eonerf_ray_layout is a second table with the same conventions, for the PER-RAY buffers a render call carves in front of its passes
+ * (n_rays rays; RAY_REC floats per record and its RR_* columns: csrc/eonerf_rays.h):
+ *
+ *   [EONERF_RAY_CNT_FIRST]     int [R]: samples of the first draw of the camera sampler
+ *   [EONERF_RAY_CNT_RETRY]     int [R]: samples of the retry draw; a call with the shadow pass leaves the shadow rays' counts here
+ *   [EONERF_RAY_FLAGS]         int [4]: bit 0 of word 0 = the retry draw was taken, as the LAST sampler launch of the call left it (the
+ *                              shadow pass' sampler never retries and overwrites the camera pass' bit)
+ *   [EONERF_RAY_REC]           fp32 [R][RAY_REC]: the per-ray record of compositing
+ *   [EONERF_RAY_G_RAY]         fp32 [R][RAY_REC]: its gradient (training layouts only)
+ *   [EONERF_RAY_AMB_SAVE]      fp32 [R][160]: sun encoding (27, padded to 32) and 128 hidden values of the ambient head (training only)
+ *   [EONERF_RAY_RAD_RAYS]      fp32 [R][6]: per-ray radiometric gradient terms (training on a deterministic context only)
+ *   [EONERF_RAY_EMB_RAYS]      fp32 [R][4]: per-ray embedding gradient sums (training on a deterministic context only)
  */
 #ifndef EONERF_LAYOUT_H
 #define EONERF_LAYOUT_H
@@ -53,6 +66,22 @@ enum {
 /* Returns EONERF_LAYOUT_ENTRIES (> 0) and fills out[0 .. EONERF_LAYOUT_ENTRIES).  EONERF_E_ARG: a null ctx / out, n < 0, an unknown kind,
  * cap < EONERF_LAYOUT_ENTRIES (nothing is written). */
 int eonerf_workspace_layout(const eonerf_ctx* ctx, int kind, int n, int flags, uint64_t* out, int cap);
+
+/* entries of eonerf_ray_layout, in the order of the carve */
+#define EONERF_RAY_CNT_FIRST 0
+#define EONERF_RAY_CNT_RETRY 1
+#define EONERF_RAY_FLAGS 2
+#define EONERF_RAY_REC 3
+#define EONERF_RAY_G_RAY 4
+#define EONERF_RAY_AMB_SAVE 5
+#define EONERF_RAY_RAD_RAYS 6
+#define EONERF_RAY_EMB_RAYS 7
+#define EONERF_RAY_ENTRIES 8
+
+/* The per-ray buffers of eonerf_render_forward / _backward(_loss) on n_rays rays with the EONERF_F_* flags of the call (also the layout of
+ * eonerf_rendering_train / _backward: EONERF_F_TRAIN, with EONERF_F_ONLY_DEPTH for depth_only).  Returns EONERF_RAY_ENTRIES (> 0) and fills
+ * out[0 .. EONERF_RAY_ENTRIES).  EONERF_E_ARG: a null ctx / out, n_rays < 0, cap < EONERF_RAY_ENTRIES (nothing is written). */
+int eonerf_ray_layout(const eonerf_ctx* ctx, int n_rays, int flags, uint64_t* out, int cap);
 
 #ifdef __cplusplus
 }

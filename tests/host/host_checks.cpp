@@ -9,7 +9,7 @@
 //   * eonerf_wgrad_plan.h: the job table and slice plan of the weight-gradient GEMM launch for every reachable combination of precision,
 //     backward path, pass set and switches -- the table fits, the items are a running sum that fits deterministic mode's partial buffer,
 //     every operand stays inside the slab block it starts in, the wave grid covers the product, the riders sit on the right job.
-//   * eonerf_layout_table.h (include/eonerf_layout.h): over the same enumeration of layouts, every offset eonerf_workspace_layout reports
+//   * eonerf_layout_table.h (include/eonerf_layout.h): over the same enumeration of layouts, every offset eonerf_workspace_layout and eonerf_ray_layout report
 //     is the carve's own pointer minus the base, a buffer the carve does not have is UINT64_MAX, and the refusals write nothing.
 // No HIP runtime call is made (GPU sanitizers are not available on this pool; the device side is covered by the parity tests).
 #include <stdio.h>
@@ -205,6 +205,20 @@ static void check_carve(const CarveCfg& cfg, int n_rays, int flags) {
     check_layout_pass("render sun", t + EONERF_LAYOUT_SUN, w.sun, base);
     for (int k = 0; k < EONERF_LAYOUT_ENTRIES; ++k)
         if (k != EONERF_LAYOUT_P_CAP && k != EONERF_LAYOUT_BYTES && t[k] != UINT64_MAX) CHECK(t[k] % 256 == 0 && t[k] < w.bytes, "layout entry %d = %llu", k, (unsigned long long)t[k]);
+    // ... and the per-ray query the buffers in front of the passes
+    uint64_t q[EONERF_RAY_ENTRIES + 1];
+    q[EONERF_RAY_ENTRIES] = 0x5a5a5a5a5a5a5a5aull;
+    CHECK(ray_layout_table(cfg, n_rays, flags, q, EONERF_RAY_ENTRIES) == EONERF_RAY_ENTRIES, "ray layout query refused");
+    CHECK(q[EONERF_RAY_ENTRIES] == 0x5a5a5a5a5a5a5a5aull, "ray layout query wrote beyond its table");
+    static_assert(EONERF_RAY_ENTRIES == 8 && EONERF_RAY_REC == 3 && EONERF_RAY_EMB_RAYS == 7, "documented order of the per-ray buffers");
+    const void* rm[EONERF_RAY_ENTRIES] = {w.cnt_first, w.cnt_retry, w.flags, w.ray_rec, w.g_ray, w.amb_save, w.det.rad_rays, w.det.emb_rays};
+    for (int k = 0; k < EONERF_RAY_ENTRIES; ++k) {
+        CHECK(q[k] == off_or_none(rm[k], base), "ray layout entry %d: query %llu, carve %llu", k, (unsigned long long)q[k], (unsigned long long)off_or_none(rm[k], base));
+        if (q[k] != UINT64_MAX) CHECK(q[k] % 256 == 0 && q[k] < w.bytes, "ray layout entry %d = %llu", k, (unsigned long long)q[k]);
+    }
+    CHECK((q[EONERF_RAY_G_RAY] != UINT64_MAX) == train && (q[EONERF_RAY_AMB_SAVE] != UINT64_MAX) == train &&
+          (q[EONERF_RAY_RAD_RAYS] != UINT64_MAX) == (train && cfg.deterministic) && (q[EONERF_RAY_EMB_RAYS] != UINT64_MAX) == (train && cfg.deterministic),
+          "ray layout query: training / deterministic buffers");
 }
 
 // eonerf_field_forward / eonerf_query_density (carve_field) and eonerf_field_forward_train / eonerf_field_backward (carve_field_train)
@@ -380,6 +394,10 @@ int main() {
         CHECK(workspace_layout_table(cfgs[1], 2, 37, 0, t, EONERF_LAYOUT_ENTRIES) == EONERF_E_ARG && t[0] == 7, "unknown kind");
         CHECK(workspace_layout_table(cfgs[1], EONERF_LAYOUT_FIELD_TRAIN, -1, 0, t, EONERF_LAYOUT_ENTRIES) == EONERF_E_ARG && t[0] == 7, "negative n");
         CHECK(workspace_layout_table(cfgs[1], EONERF_LAYOUT_RENDER, 37, 0, nullptr, EONERF_LAYOUT_ENTRIES) == EONERF_E_ARG, "null table");
+        uint64_t q[EONERF_RAY_ENTRIES] = {7};
+        CHECK(ray_layout_table(cfgs[1], 37, EONERF_F_TRAIN, q, EONERF_RAY_ENTRIES - 1) == EONERF_E_ARG && q[0] == 7, "ray layout: short table");
+        CHECK(ray_layout_table(cfgs[1], -1, 0, q, EONERF_RAY_ENTRIES) == EONERF_E_ARG && q[0] == 7, "ray layout: negative n");
+        CHECK(ray_layout_table(cfgs[1], 37, 0, nullptr, EONERF_RAY_ENTRIES) == EONERF_E_ARG, "ray layout: null table");
     }
     check_wgrad_plans();
     if (g_fail) { fprintf(stderr, "%d check(s) failed\n", g_fail); return 1; }
