@@ -233,6 +233,19 @@ API_STAGED_TEXTURE = {
     },
 }
 
+# And a fifth (the four staged ABI tests pin the tables above); tests/test_dual_abi_cpu.py holds it to the header.  lib() binds it after
+# API_STAGED_TEXTURE.
+API_STAGED_DUAL = {
+    # dual contouring of a volume from Hermite data (mesh.dual_contour, mesh.extract_mesh(method="dual"))
+    "eonerf_dual.h": {
+        "eonerf_dual_version": (i, []),
+        "eonerf_dual_workspace_bytes": (sz, [i, i, i]),
+        "eonerf_dual_count": (i, [vp, i, i, i, fp, vp, vp, sz, vp]),
+        "eonerf_dual_hermite": (i, [vp, i, i, i, fp, f3, f3, vp, sz, vp, i64, vp, vp, vp]),
+        "eonerf_dual_emit": (i, [vp, i, i, i, fp, f3, f3, vp, i64, fp, vp, sz, vp, i64, vp, vp, i64, vp, vp, vp]),
+    },
+}
+
 
 def build(verbose=False):
     """Compile libeonerf_hip.so in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
@@ -284,7 +297,7 @@ def lib():
                            "(the EO-NeRF hot path has no non-HIP fallback)")
     L = C.CDLL(LIB_PATH)
     for group in (list(API.values()) + list(API_STAGED.values()) + list(API_STAGED_SMOOTH.values()) + list(API_STAGED_RAYCAST.values())
-                  + list(API_STAGED_TEXTURE.values())):
+                  + list(API_STAGED_TEXTURE.values()) + list(API_STAGED_DUAL.values())):
         for name, (restype, argtypes) in group.items():
             fn = getattr(L, name)               # resolves the symbol: a missing one fails here, at load
             fn.restype, fn.argtypes = restype, argtypes

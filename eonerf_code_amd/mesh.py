@@ -36,12 +36,20 @@ through a uniform grid that may not change a bit of it.  render_mesh gives the d
 the scale of render_image's depth, per-vertex tables interpolated there, and the hard shadow of that image's sun; vertex_visibility says
 which vertices a sun or a satellite sees.  The default grid and both bias defaults are guesses (profiles/raycast_ab.txt has what was measured).
 
-Not here: a BVH or any structure for meshes that do not fit a uniform grid, perspective cameras other than ray tables, anti-aliasing, texture atlases, a loss on the
+dual_contour (csrc/eonerf_dual.h, a staged header) is the second mesher: one vertex per cell the surface crosses, placed by minimising
+the quadric of the planes through the crossing points of the cell's edges with the field's gradient there as normal, and one quad per
+sign-changing lattice edge, so that vertices can sit on ridges and corners inside a cell and a surface takes about a third of marching
+tetrahedra's triangles.  It returns the same kind of mesh, so everything above takes it as it is; extract_mesh(method="dual") runs it
+with normals.density_gradient at the Hermite points.  Marching tetrahedra stay the default; the default regularisation 0.1 is a guess.
+
+Not here: choosing a quad's diagonal by the Hermite normals, manifold dual contouring, per-vertex component ids of a dual mesh, adaptive
+(octree) cells, intersection-free guarantees, a BVH or any structure for meshes that do not fit a uniform grid, perspective cameras other than ray tables, anti-aliasing, texture atlases, a loss on the
 mesh's shadows, cotangent or area weights, bilateral or feature-preserving filters, implicit smoothing, re-projection onto the level set,
 sliding open vertices along their boundary, marching cubes, vertex refinement along the gradient, filters on area or height above ground, labelling of the mesh graph
 itself, edge collapse, quadric error representatives, welding by distance, removal of duplicate triangles, textures, skipping empty space through the occupancy grid while the volume is filled, volumes larger
 than one call, OBJ / glTF writers.
 The default level of extract_mesh is a guess: it has not been measured on a converged scene, and neither has the quality of the mesh.
+So is the default regularisation of dual_contour and extract_mesh(method="dual"), 0.1 (profiles/dual_ab.txt has what was measured).
 """
 import ctypes as C
 import math
@@ -161,6 +169,81 @@ def mesh_from_volume(volume, level, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1
         raise RuntimeError("mesh_from_volume: the emit call found more vertices or triangles than the count call (the volume changed in between?)")
     out = (vertices[:n_v], faces[:n_t])
     return out + (keys[:n_v],) if return_keys else out
+
+
+DUAL_MIN_REGULARISATION, DUAL_MAX_REGULARISATION = 2.0 ** -10, 16.0      # EONERF_DUAL_MIN_REG_LOG2, EONERF_DUAL_MAX_REG_LOG2
+DUAL_REGULARISATION = 0.1           # the default lambda of dual_contour and extract_mesh(method="dual"): a guess, not measured
+DUAL_REPORT = ("clamped", "fallback", "dropped_planes")
+MESH_METHODS = ("tetra", "dual")
+
+
+@torch.no_grad()
+def dual_contour(volume, level, gradient, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0), regularisation=DUAL_REGULARISATION, return_keys=False,
+                 chunk=1 << 20):
+    """Level set `level` of volume [nz, ny, nx] (fp32, on the device; lattice point (i, j, k) at origin + spacing * (i, j, k)) by dual
+    contouring, the rule of csrc/eonerf_dual.h (a staged header): one vertex per cell the surface crosses, placed in the cell by
+    minimising the quadric of the planes through the crossing points of the cell's edges (the Hermite points) with the field's gradient
+    there as normal, and two triangles per sign-changing lattice edge.  Vertices can therefore sit on a ridge or a corner inside a
+    cell, which marching tetrahedra cut off.  Inside is volume >= level; face normals point out of it.  Nothing is welded; every edge
+    is shared by an even number of triangles, but the mesh is NOT promised to be a 2-manifold.  Bit-reproducible.
+    gradient: a callable points fp32 [n, 3] -> fp32 [n, 3] (asked in chunks of at most `chunk` Hermite points, in the volume's
+    coordinates; for a field: lambda p: normals.density_gradient(field, p)[1]), or a tensor [H, 3], row h for Hermite point h.  Its
+    sign and length do not matter; rows that are zero or not finite are left out of their cells' quadrics and counted.
+    regularisation: lambda, the pull towards the mean of a cell's Hermite points in lattice spacings, in [2^-10, 16].  The default 0.1
+    is a guess: it has not been measured on a converged scene.
+    Returns (vertices fp32 [V, 3], faces int32 [T, 3], report): report = {"hermite", "vertices", "faces", "nonfinite_edges",
+    "clamped" (vertices the solve put outside their cell, held on its wall), "fallback" (vertices left at the mean: a solve that was
+    not finite), "dropped_planes", "regularisation"}.  return_keys: also (cell_keys int64 [V]: each vertex' cell index, hermite fp32
+    [H, 3]: the Hermite points, hermite_keys int64 [H]: lattice point * 8 + axis).
+    Two host synchronisations: the read-back of the counts between the count and the other calls, and of status and report at the end."""
+    if volume.dim() != 3 or volume.device.type != "cuda":
+        raise ValueError("volume must be a [nz, ny, nx] tensor on the GPU (the extraction has no host form)")
+    lam = float(regularisation)
+    if not (math.isfinite(lam) and DUAL_MIN_REGULARISATION <= lam <= DUAL_MAX_REGULARISATION):
+        raise ValueError(f"regularisation={regularisation!r}: finite and in [2^-10, 16]")
+    vol = volume.detach().float().contiguous()
+    nz, ny, nx = vol.shape
+    origin = origin if isinstance(origin, C.Array) else _f3(origin, "origin")
+    spacing = spacing if isinstance(spacing, C.Array) else _f3(spacing, "spacing")
+    level = float(level)
+    dev = vol.device
+    L = _lib.lib()
+    nb = L.eonerf_dual_workspace_bytes(nx, ny, nz)
+    if not nb:
+        raise ValueError(f"a {nz} x {ny} x {nx} volume: every dimension must be at least 2 and one call takes 2^28 points")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        _lib.check(L.eonerf_dual_count(_ptr(vol), nx, ny, nz, level, _ptr(counts), _ptr(ws), nb, _stream()))
+        n_h, n_v, n_t, n_bad = counts.tolist()         # the export's host synchronisation
+        if n_bad:
+            import warnings
+            warnings.warn(f"dual_contour: {n_bad} crossing edge(s) have an end that is not finite; their Hermite points sit at the edge's middle")
+        back = torch.zeros(6, dtype=torch.int64, device=dev)           # report[4], then the two status words in the low halves of two more
+        points = torch.empty(max(n_h, 1), 3, dtype=torch.float32, device=dev)
+        point_keys = torch.empty(max(n_h, 1), dtype=torch.int64, device=dev) if return_keys else None
+        _lib.check(L.eonerf_dual_hermite(_ptr(vol), nx, ny, nz, level, origin, spacing, _ptr(ws), nb, _ptr(points), n_h, _ptr(point_keys),
+                                         C.c_void_p(back.data_ptr() + 32), _stream()))
+        if callable(gradient):
+            parts = [gradient(points[i:i + chunk]) for i in range(0, n_h, chunk)]
+            table = torch.cat(parts, dim=0) if parts else points.new_empty(0, 3)
+        else:
+            table = gradient
+        table = torch.as_tensor(table).detach().to(dev, torch.float32).reshape(-1, 3).contiguous()
+        if table.shape[0] != n_h:
+            raise ValueError(f"gradient: one row per Hermite point, {n_h} x 3, not {tuple(table.shape)}")
+        g_in = table if n_h else torch.zeros(1, 3, dtype=torch.float32, device=dev)          # the library takes no null pointer
+        vertices = torch.empty(max(n_v, 1), 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(max(n_t, 1), 3, dtype=torch.int32, device=dev)
+        cell_keys = torch.empty(max(n_v, 1), dtype=torch.int64, device=dev) if return_keys else None
+        _lib.check(L.eonerf_dual_emit(_ptr(vol), nx, ny, nz, level, origin, spacing, _ptr(g_in), n_h, lam, _ptr(ws), nb, _ptr(vertices), n_v,
+                                      _ptr(cell_keys), _ptr(faces), n_t, _ptr(back), C.c_void_p(back.data_ptr() + 40), _stream()))
+        numbers = back.tolist()                                        # the second host synchronisation
+    if (numbers[4] | numbers[5]) & STATUS_CAPACITY:
+        raise RuntimeError("dual_contour: a later call found more Hermite points, vertices or triangles than the count call (the volume changed in between?)")
+    report = {"hermite": n_h, "vertices": n_v, "faces": n_t, "nonfinite_edges": n_bad, **dict(zip(DUAL_REPORT, numbers[:3])), "regularisation": lam}
+    out = (vertices[:n_v], faces[:n_t], report)
+    return out + (cell_keys[:n_v], points[:n_h], point_keys[:n_h]) if return_keys else out
 
 
 SIDES = {"inside": 0, "outside": 1, 0: 0, 1: 1}
@@ -301,7 +384,8 @@ class MeshDict(dict):
 @torch.no_grad()
 def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offset=None, scene_scale=None, normals=True, albedo=True,
                  slab_points=1 << 22, chunk=1 << 20, min_component_points=0, keep_largest=0, protect_boundary=False, fill_cavities=False,
-                 components=False, simplify=0, representative="mean", smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
+                 components=False, simplify=0, representative="mean", smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, method="tetra",
+                 dual_regularisation=DUAL_REGULARISATION):
     """Mesh of the level set `level` of the field's density on a resolution^3 lattice over `bounds` (scene coordinates: the normalised
     cube).  Returns a dict: "vertices" fp32 [V, 3] in scene coordinates; "faces" int32 [T, 3], normals out of the dense side; "level";
     "normals" fp32 [V, 3]: -grad sigma at the vertices (normals.density_gradient, times 1 / scene_scale when that is given: the metric
@@ -320,8 +404,17 @@ def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offs
     smooth=k > 0: k lambda|mu iterations of smooth_mesh (factors smooth_lambda, smooth_mu; units of one lattice spacing) move the
     extracted vertices after the component ids are taken and BEFORE simplify, normals and albedo, which the field then gives at the moved
     vertices.  The dict then also carries "smooth" (smooth_mesh's report).  0: no smoothing call is made and the result keeps today's
-    bits and keys."""
+    bits and keys.
+    method: "tetra" (the default, and what an omitted argument gives, bit for bit) -- marching tetrahedra, mesh_from_volume -- or "dual"
+    -- dual_contour on the same (filtered) volume with normals.density_gradient at the Hermite points, asked in chunks of `chunk`, and
+    lambda = dual_regularisation (default 0.1: a guess, not measured).  Everything behind the mesher runs unchanged on either mesh;
+    the dict of "dual" also carries "dual" (dual_contour's report).  components=True with "dual" raises ValueError: a cell can touch
+    two solids, so a per-vertex component id is not defined there."""
     from .normals import _axis_scale, density_gradient
+    if method not in MESH_METHODS:
+        raise ValueError(f"method={method!r}: one of {MESH_METHODS}")
+    if method == "dual" and components:
+        raise ValueError("components=True with method='dual': a dual-contouring vertex belongs to a cell, which can touch two solids; per-vertex ids are not defined")
     if level is None:
         level = level_from_opacity(0.5, 2.0 / 128)
     shape = (int(resolution),) * 3 if isinstance(resolution, int) else tuple(resolution)
@@ -330,7 +423,10 @@ def extract_mesh(field, resolution=256, level=None, bounds=UNIT_CUBE, scene_offs
     cleanup = {}
     if min_component_points or keep_largest or fill_cavities:
         volume, cleanup["report"] = filter_components(volume, level, min_component_points, keep_largest, protect_boundary, fill_cavities)
-    if components:
+    if method == "dual":
+        vertices, faces, cleanup["dual"] = dual_contour(volume, level, lambda points: density_gradient(field, points)[1], origin, spacing,
+                                                        regularisation=dual_regularisation, chunk=chunk)
+    elif components:
         vertices, faces, keys = mesh_from_volume(volume, level, origin, spacing, return_keys=True)
         labels, info, _ = label_components(volume, level)
         cleanup["component"] = vertex_components(keys, labels)

@@ -47,7 +47,11 @@ and `--mesh_smooth_mu M`, defaults 0.5 and -0.53) runs K lambda|mu iterations of
 the extracted mesh, before the simplification, the normals and the albedo (mesh.smooth_mesh); it moves vertices and keeps every vertex
 and face, vertices on an open boundary stay put, and the status line then ends in `smooth=K | open=N`, N the open vertices.  It is off
 by default -- what it does to the DSM MAE is a measurement in profiles/smooth_ab.txt, not a default -- and acts only together with
-`--mesh_out`.  Together with `--gt_dsm` rank 0 then rasterises
+`--mesh_out`.  `--mesh_method tetra|dual` (default tetra) chooses the mesher: marching tetrahedra, or dual contouring
+(mesh.dual_contour: one vertex per surface cell from the density gradient at the crossing points of its edges, which keeps ridges and
+corners, at about a third of the triangles) with `--mesh_dual_reg L` as its regularisation (default 0.1, a guess that has not been
+measured); the three component flags still filter the volume in front of it, but a dual mesh carries no per-vertex component id,
+and the status line then ends in `method=dual | clamped=N`.  It acts only together with `--mesh_out`.  Together with `--gt_dsm` rank 0 then rasterises
 the mesh it saved (filtered, smoothed, simplified) straight from above on the lidar DSM's grid, registers it and prints `mesh/mae=` once
 (eonerf_code_amd.mesh.evaluate_mesh_dsm): the mesh on the scale of val/mae.  Without the flag nothing changes.
 `--mesh_views` (with `--mesh_out` and `--val_images`; refused without them) casts the rays of every held-out image against the saved
@@ -117,6 +121,8 @@ def main():
     ap.add_argument("--mesh_smooth", type=int, default=0, help="lambda|mu iterations of Taubin smoothing on the extracted mesh (0: off; only with --mesh_out)")
     ap.add_argument("--mesh_smooth_lambda", type=float, default=0.5, help="the positive factor of a smoothing iteration")
     ap.add_argument("--mesh_smooth_mu", type=float, default=-0.53, help="the negative factor of a smoothing iteration (0: plain Laplacian)")
+    ap.add_argument("--mesh_method", choices=["tetra", "dual"], default="tetra", help="the mesher: marching tetrahedra or dual contouring (only with --mesh_out)")
+    ap.add_argument("--mesh_dual_reg", type=float, default=0.1, help="regularisation of --mesh_method dual, in lattice spacings (2^-10 .. 16)")
     ap.add_argument("--mesh_views", action="store_true",
                     help="cast every --val_images view's rays against the saved mesh: depth against the field's, hits, shadow agreement (only with --mesh_out and --val_images)")
     ap.add_argument("--mesh_texture", default=None, help="torch file in the format of --ortho: bake the images onto the saved mesh, write <stem>.obj/.mtl/.png (only with --mesh_out)")
@@ -280,16 +286,19 @@ def main():
                     from .mesh import extract_mesh, save_ply
                     cleaned = bool(args.mesh_min_component or args.mesh_keep_largest or args.mesh_fill_cavities)
                     mesh = extract_mesh(field, resolution=args.mesh_res, level=args.mesh_level, min_component_points=args.mesh_min_component,
-                                        keep_largest=args.mesh_keep_largest, fill_cavities=args.mesh_fill_cavities, components=cleaned,
+                                        keep_largest=args.mesh_keep_largest, fill_cavities=args.mesh_fill_cavities,
+                                        components=cleaned and args.mesh_method == "tetra",
                                         simplify=args.mesh_simplify, representative=args.mesh_representative, smooth=args.mesh_smooth,
-                                        smooth_lambda=args.mesh_smooth_lambda, smooth_mu=args.mesh_smooth_mu)
+                                        smooth_lambda=args.mesh_smooth_lambda, smooth_mu=args.mesh_smooth_mu, method=args.mesh_method,
+                                        dual_regularisation=args.mesh_dual_reg)
                     os.makedirs(os.path.dirname(os.path.abspath(args.mesh_out)), exist_ok=True)
                     save_ply(args.mesh_out, mesh)
                     print(f"step={step} | mesh={args.mesh_out} | vertices={mesh['vertices'].shape[0]} | faces={mesh['faces'].shape[0]} | "
                           f"level={mesh['level']:.6g}" +
                           (f" | vertices_in={mesh['simplify']['vertices_in']} | faces_in={mesh['simplify']['faces_in']}" if args.mesh_simplify else "") +
-                          (f" | smooth={args.mesh_smooth} | open={mesh['smooth']['open']}" if args.mesh_smooth else ""), flush=True)
-                    if cleaned:
+                          (f" | smooth={args.mesh_smooth} | open={mesh['smooth']['open']}" if args.mesh_smooth else "") +
+                          (f" | method=dual | clamped={mesh['dual']['clamped']}" if args.mesh_method == "dual" else ""), flush=True)
+                    if cleaned and "component" in mesh:
                         sizes = mesh["component_points"]
                         print(f"step={step} | mesh_components={int(torch.unique(mesh['component']).numel())} | "
                               f"smallest_component={int(sizes.min()) if sizes.numel() else 0} | " +
